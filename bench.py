@@ -14,7 +14,16 @@ Synthetic corpus: LDA generative process, drawn on the GPU.
 Prints ONE JSON line (rank 0).  value = tokens sampled by all ranks per
 second of the max-over-ranks wall time of the K timed sweeps.
 
+A plain run does what that figure needs and no more: it draws the corpus,
+warms up, times the K sweeps, writes its outputs (--dump-outputs DIR) and
+prints the headline line.  --full adds every side figure and check to the
+line: the roofline block (per-launch kernel times, PMC traffic record, issue
+bound, measured copy rate), the replica check and LL/token, the collective
+block (N > 1), the drop-in's sweep schedule, ParallelTopicModel.estimate()
+on the C4 shard and the cpu_mallet baseline.
+
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c1|c2|c3|c5]
+                  [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -442,6 +451,42 @@ def dropin_schedule(args, sampler, trainer, world, device, tokens_all):
         sampler.set_sequential_sweeps(1)
 
 
+DUMP_NW_BYTES = 32 << 20      # --dump-outputs: float64 cells of nw kept
+DUMP_Z_TOKENS = 2 << 20       # --dump-outputs: float32 topics of z kept
+
+
+def dump_outputs(path: str, sampler, rank: int = 0, world: int = 1, seed: int = 20261015):
+    """--dump-outputs: the sampler state a caller of the timed path holds after
+    its last sweep, as <path>/<name>.npy (under 64 MB in all):
+      nwsum     float64 [K]        tokens per topic (whole)
+      nw        float64 [R, K]     word-topic counts: every row when V K cells
+                                   fit DUMP_NW_BYTES, else the rows nw_rows
+      nw_rows   float64 [R]        the rows of nw kept (sorted; seeded draw)
+      z         float32 [n]        topic assignments: all N when N <=
+                                   DUMP_Z_TOKENS, else at seeded token positions
+    The counts are the replica every rank holds, so rank 0 writes them; z is
+    the rank's own shard (z_rank<r>.npy for N > 1).  The draws depend only on
+    `seed` and the shapes, so two builds dump the same cells."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    rows = np.arange(sampler.V)
+    keep = max(1, DUMP_NW_BYTES // (8 * sampler.K))
+    if keep < sampler.V:
+        rows = np.sort(rng.choice(sampler.V, size=keep, replace=False))
+    at = None
+    if sampler.N > DUMP_Z_TOKENS:
+        at = np.sort(rng.integers(0, sampler.N, size=DUMP_Z_TOKENS))
+    if rank == 0:
+        nw, nwsum, _, _ = sampler.counts()
+        np.save(os.path.join(path, "nwsum.npy"), nwsum.astype(np.float64))
+        np.save(os.path.join(path, "nw.npy"), nw[rows].astype(np.float64))
+        np.save(os.path.join(path, "nw_rows.npy"), rows.astype(np.float64))
+        del nw
+    z = sampler.z()
+    np.save(os.path.join(path, "z.npy" if world == 1 else f"z_rank{rank}.npy"),
+            (z if at is None else z[at]).astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -454,7 +499,15 @@ def main():
                     help="draw kernel (default: dense, sparse for c5)")
     ap.add_argument("--burnin", type=int, default=0,
                     help="extra untimed sweeps before the warm-up (steady-state measurement)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure (roofline, "
+                         "replica check, LL, drop-in schedule, estimate() side figure, CPU "
+                         "baseline); a plain run only times the sweeps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed sweeps, write the sampler's state (counts, topic "
+                         "assignments; seeded samples of the large ones) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the cpu_mallet baseline")
     ap.add_argument("--tokens-per-range", type=int, default=0,
                     help="work-queue granule (0 = the library's default)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -462,8 +515,8 @@ def main():
                          "rehearse several ranks on one GPU)")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     ap.add_argument("--no-estimate", action="store_true",
-                    help="skip the side figure: ParallelTopicModel.estimate() on the C4 shard "
-                         "(N=1, c4 / c4shard only)")
+                    help="--full without the side figure: ParallelTopicModel.estimate() on the C4 "
+                         "shard (N=1, c4 / c4shard only)")
     ap.add_argument("--exchange-parts", type=int, default=None,
                     help="N > 1: split every sweep into P parts whose all-reduces overlap the "
                          "next part's sampling (default 1: DESIGN.md §5)")
@@ -479,7 +532,7 @@ def main():
                          "pack, the in-place all-reduce, the all-gather and the unpack, whose sum "
                          "is the identity) to price the exchange's on-GPU cost; never the default")
     ap.add_argument("--dropin-steps", type=int, default=5,
-                    help="after the timed region, time this many sweeps under the Java drop-in's "
+                    help="--full: after the timed region, time this many sweeps under the Java drop-in's "
                          "default schedule (Mallet's 4-thread staleness: two sequential parts, "
                          "each exchanged when N > 1; DESIGN.md §2, §5); 0 = skip")
     ap.add_argument("--reserve-cus", type=int, default=-1,
@@ -596,7 +649,7 @@ def main():
     for _ in range(args.burnin + args.warmup):
         step()
     torch.cuda.synchronize()
-    nnz0 = sampler.row_stats() if args.sampler == "sparse" and rank == 0 else None
+    nnz0 = sampler.row_stats() if args.full and args.sampler == "sparse" and rank == 0 else None
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -607,7 +660,61 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0
+    elapsed = elapsed_rank = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sampler, rank, world)
+    t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{device}")
+    if world > 1:
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    elapsed = float(t.item())
+    nt = torch.tensor([n_local], dtype=torch.int64, device=f"cuda:{device}")
+    if world > 1:
+        dist.all_reduce(nt, op=dist.ReduceOp.SUM)
+    tokens_all = int(nt.item())
+    total_tokens = tokens_all * args.steps
+    value = total_tokens / elapsed
+    headline = {
+        "metric": f"Gibbs tokens sampled/sec at K={K}",
+        "value": value,
+        "unit": "tokens/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "burnin": args.burnin,
+        "sampler": args.sampler,
+        "ms_per_step": elapsed * 1e3 / args.steps,
+        "higher_is_better": True,
+        "scaling": cfg.get("scaling", "weak"),
+        "vs_baseline": None,
+        "dtype": "fp32 weights / int32 counts",
+        "data": ("synthetic (changelist-shaped inverse_docs corpus, SURVEY.md §8d; corpus.synthetic_changelists)"
+                 if args.config.startswith("c1") else
+                 "synthetic (LDA generative process, SURVEY.md §8d; phi~Dir(0.01), theta~Dir(0.1))"),
+        "config": {
+            "workload": cfg["desc"],
+            "docs_per_gpu": docs,
+            "doc_len": L,
+            "tokens_per_gpu": n_local,
+            "tokens_all_gpus": tokens_all,
+            "corpus_blocks": blocks_info,
+            "num_types": V,
+            "num_topics": K,
+            "alpha_sum": alpha_sum,
+            "beta": beta,
+            "parallelism": f"dp{world} (AD-LDA doc shards, "
+                           f"{'RCCL' if args.backend == 'nccl' else 'gloo'} all-reduce of int32 delta)",
+        },
+        "full": args.full,
+        "corpus_gen_s": t_gen,
+    }
+    if not args.full:
+        # the plain run ends here: every other figure and check is --full's
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        sampler.close()
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
     # per-launch duration of the sampler kernel over the timed region: HIP
     # events recorded around every launch on the sampler's stream, read back
     # after the closing synchronize (no host sync inside the timed loop)
@@ -629,17 +736,7 @@ def main():
     # every rank's replica of nw / nwsum must be identical after the timed
     # region (lda_counts_checksum + the LL's word part, MIN == MAX over the
     # ranks), and the ranks' own timed-region seconds travel with the line
-    replicas = trainer.replica_check(seconds=elapsed)
-    t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{device}")
-    if world > 1:
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    elapsed = float(t.item())
-    nt = torch.tensor([n_local], dtype=torch.int64, device=f"cuda:{device}")
-    if world > 1:
-        dist.all_reduce(nt, op=dist.ReduceOp.SUM)
-    tokens_all = int(nt.item())
-    total_tokens = tokens_all * args.steps
-    value = total_tokens / elapsed
+    replicas = trainer.replica_check(seconds=elapsed_rank)
     ll = trainer.log_likelihood()
     dropin = None
     if args.dropin_steps > 0:
@@ -747,36 +844,7 @@ def main():
                                            "pack + unpack kernels and RCCL's one-rank calls, not a "
                                            "transfer")
         result = {
-            "metric": f"Gibbs tokens sampled/sec at K={K}",
-            "value": value,
-            "unit": "tokens/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "burnin": args.burnin,
-            "sampler": args.sampler,
-            "ms_per_step": elapsed * 1e3 / args.steps,
-            "higher_is_better": True,
-            "scaling": cfg.get("scaling", "weak"),
-            "vs_baseline": None,
-            "dtype": "fp32 weights / int32 counts",
-            "data": ("synthetic (changelist-shaped inverse_docs corpus, SURVEY.md §8d; corpus.synthetic_changelists)"
-                     if args.config.startswith("c1") else
-                     "synthetic (LDA generative process, SURVEY.md §8d; phi~Dir(0.01), theta~Dir(0.1))"),
-            "config": {
-                "workload": cfg["desc"],
-                "docs_per_gpu": docs,
-                "doc_len": L,
-                "tokens_per_gpu": n_local,
-                "tokens_all_gpus": tokens_all,
-                "corpus_blocks": blocks_info,
-                "num_types": V,
-                "num_topics": K,
-                "alpha_sum": alpha_sum,
-                "beta": beta,
-                "parallelism": f"dp{world} (AD-LDA doc shards, "
-                               f"{'RCCL' if args.backend == 'nccl' else 'gloo'} all-reduce of int32 delta)",
-            },
+            **headline,
             "roofline": {
                 "bound": bound,
                 "bound_detail": bound_detail,
@@ -827,7 +895,6 @@ def main():
             "collective": coll,
             "dropin_schedule": dropin,
             "ll_per_token": ll / tokens_all,
-            "corpus_gen_s": t_gen,
         }
         if nnz0 is not None:
             result["roofline"]["mean_row_nnz"] = [nnz0, nnz1]
