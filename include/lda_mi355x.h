@@ -362,6 +362,36 @@ lda_status lda_infer(lda_ctx* ctx, int64_t Dh, const int64_t* doc_off, const int
                      int32_t num_iterations, int32_t thinning, int32_t burn_in, uint64_t seed,
                      double* theta);
 
+/* The reference's prediction step [src/cmu_ron/TrainAndPredict.java
+ * Predictor.predict + Metrics.cosineSimilarity; src/cmu/TrainAndPredict.java
+ * scoresForChangelistOnTests], batched: the similarity of Q topic
+ * distributions theta[Q*K] (rows of lda_infer, or any non-negative rows; they
+ * need not sum to 1) to the topic distribution of documents of THIS shard,
+ *     p_d[k] = (n_dk + alpha_k) / (n_d + sum alpha),
+ * what ParallelTopicModel.getTopicProbabilities returns, from the shard's
+ * current z on the device.
+ *  LDA_SCORE_COSINE  p_d . theta_q / (|p_d| |theta_q|)
+ *  LDA_SCORE_MSE     sum_k (p_d[k] - theta_q[k])^2 / K
+ * docs == NULL: documents [doc_begin, doc_begin + M); else docs[M] shard-local
+ * ids in any order, duplicates allowed (doc_begin must be 0).  scores[Q*M]
+ * row-major (scores[q*M + j] for the j-th document), fp64.  An empty document
+ * scores as p_d = alpha / sum alpha.  Every sum is a fixed-order fp64
+ * reduction: a call repeats bit for bit, and a document's scores do not
+ * depend on M, docs or the shard's other documents.
+ * Errors: LDA_ERR_STATE with a pending delta (call lda_apply first);
+ * LDA_ERR_INVALID_ARG for an unknown metric, a document id or range outside
+ * [0, D), a theta row with a negative or non-finite entry, or a theta row
+ * that sums to zero.  Q = 0 or M = 0 succeeds and touches nothing.
+ * Device scratch is grow-only and kept by the context.  The work is cut into
+ * chunks of at most 1024 queries x 2^22 / min(Q, 1024) documents, so the
+ * scratch never exceeds 32 MiB of scores + 32 MiB of document ids (docs
+ * given) + 1024 (K + 2) doubles of queries (<= 32.1 MiB), whatever Q and M
+ * are.  Waits for the context's stream. */
+#define LDA_SCORE_COSINE 0
+#define LDA_SCORE_MSE 1
+lda_status lda_score_docs(lda_ctx* ctx, int32_t metric, int64_t Q, const double* theta,
+                          int64_t doc_begin, int64_t M, const int64_t* docs, double* scores);
+
 /* Mallet-layout adapter: typeTopicCounts as packed (count << topic_bits) |
  * topic rows sorted descending, rows[row_off[w] .. row_off[w+1]) with
  * row_off[V+1]; row length = min(K, typeTotal[w]) exactly as Mallet allocates
@@ -466,8 +496,8 @@ void lda_debug_fail_host_alloc(int32_t nth);
  * large-K sampler's draw (C >= 32: exact fixed-point doc part, own-entry
  * accept / re-draw), sequential sweeps recount under LDA_COUNT_RECOUNT,
  * lda_exchange_unpack_lists, lda_counts_checksum; 7 -- lda_set_exchange_cells
- * (four 8-bit cells per packed word). */
-#define LDA_ABI_VERSION 7
+ * (four 8-bit cells per packed word); 8 -- lda_score_docs. */
+#define LDA_ABI_VERSION 8
 const char* lda_version(void);
 int32_t lda_abi_version(void);
 

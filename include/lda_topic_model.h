@@ -16,6 +16,8 @@
  *   printDocumentTopics(File)                     -> ldatm_print_document_topics
  *   printTopWords(File, n, newLines)              -> ldatm_print_top_words
  *   getInferencer().getSampledDistribution(...)   -> ldatm_infer
+ *   the predict loop's similarity to every
+ *   training document (Predictor.predict)        -> ldatm_score / ldatm_score_theta / ldatm_score_top
  * Word ids index the model's alphabet (Mallet's Alphabet: insertion order).
  * Errors: lda_status codes of lda_mi355x.h, message in ldatm_last_error().
  */
@@ -170,6 +172,41 @@ lda_status ldatm_load(ldatm** out, const char* path);
 lda_status ldatm_infer(ldatm* m, int64_t Dh, const int64_t* doc_off, const int32_t* words,
                        int32_t num_iterations, int32_t thinning, int32_t burn_in, uint64_t seed,
                        double* theta);
+
+/* Prediction scoring: the reference compares a changelist's inferred
+ * distribution with getTopicProbabilities of every training document
+ * [src/cmu_ron/TrainAndPredict.java Predictor.predict with
+ * Metrics.cosineSimilarity; src/cmu/TrainAndPredict.java
+ * scoresForChangelistOnTests, whose "mse" is taken as the mean squared
+ * difference it evidently means].  Here that is one batched call per shard on
+ * the device (lda_score_docs; metric LDA_SCORE_COSINE / LDA_SCORE_MSE); no
+ * copy of z and no Q x D x K loop on the host.
+ *
+ * ldatm_score_theta: precomputed distributions theta[Q*K] against the global
+ * document ids docs[M] (any order, duplicates allowed), or docs == NULL: all
+ * documents, M = the model's D.  scores[Q*M] row-major.  Global ids are mapped
+ * onto the shards' document ranges; each shard scores its own documents on
+ * its own device and stream and the results are scattered back into the
+ * caller's order; they do not depend on the number of shards, bit for bit.
+ * Errors: LDA_ERR_INVALID_ARG for a NULL model or scores, an unknown metric, a
+ * document id outside [0, D), M != D without a list, or a theta row with a
+ * negative / non-finite entry or a zero sum.  Q = 0 or M = 0 succeeds. */
+lda_status ldatm_score_theta(ldatm* m, int32_t metric, int64_t Q, const double* theta,
+                             int64_t M, const int64_t* docs, double* scores);
+/* ldatm_infer (same arguments) followed by ldatm_score_theta of its result:
+ * scores[Dh*M]; theta_out[Dh*K] receives the inferred distributions when not
+ * NULL. */
+lda_status ldatm_score(ldatm* m, int32_t metric, int64_t Dh, const int64_t* doc_off, const int32_t* words,
+                       int32_t num_iterations, int32_t thinning, int32_t burn_in, uint64_t seed,
+                       int64_t M, const int64_t* docs, double* scores, double* theta_out);
+/* The n best documents of the whole model per query: doc_ids[Q*n] (global
+ * ids) and scores[Q*n], best first -- the largest cosine, the smallest mse --
+ * equal scores by ascending document id.  Scored shard by shard in chunks of
+ * at most 2^22 scores; the n best per query are kept on the host.  With n
+ * above D the first D entries are filled and the rest are id -1, score NaN.
+ * Errors as ldatm_score_theta (NULL doc_ids / scores, n < 0: INVALID_ARG). */
+lda_status ldatm_score_top(ldatm* m, int32_t metric, int64_t Q, const double* theta, int32_t n,
+                           int64_t* doc_ids, double* scores);
 
 /* The number renderings of Mallet's text outputs (host-only): style 0 =
  * Double.toString (printDocumentTopics weights), 1 = NumberFormat with at

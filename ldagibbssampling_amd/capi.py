@@ -30,6 +30,28 @@ MAX_DOC_TOKENS_BIGK = 65535
 MAX_EXCHANGE_PARTS = 4
 SAMPLERS = {"dense": 0, "sparse": 1}
 COUNT_UPDATE = {"auto": 0, "recount": 1, "delta": 2}
+SCORE_METRICS = {"cosine": 0, "mse": 1}
+
+
+def score_metric(metric) -> int:
+    """LDA_SCORE_* of a metric name; an integer passes through, so that an
+    unknown one reaches the library's own check."""
+    if isinstance(metric, str):
+        if metric not in SCORE_METRICS:
+            raise ValueError(f"metric must be one of {sorted(SCORE_METRICS)}, not {metric!r}")
+        return SCORE_METRICS[metric]
+    return int(metric)
+
+
+def as_theta(theta, K: int) -> np.ndarray:
+    """theta as a C-contiguous fp64 [Q, K] array (a single row becomes Q = 1);
+    a wrong shape is refused before any native call."""
+    t = np.asarray(theta, dtype=np.float64)
+    if t.ndim == 1:
+        t = t[None, :]
+    if t.ndim != 2 or t.shape[1] != K:
+        raise ValueError(f"theta must have shape [Q, {K}], not {list(np.shape(theta))}")
+    return np.ascontiguousarray(t)
 
 
 class LdaError(RuntimeError):
@@ -89,6 +111,7 @@ SIGNATURES = {
                                                C.POINTER(C.c_double)]),
     "lda_infer": (C.c_int32, [_vp, C.c_int64, _i64p, _i32p, C.c_int32, C.c_int32, C.c_int32,
                               C.c_uint64, _f64p]),
+    "lda_score_docs": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_int64, _vp, _vp]),
     "lda_to_mallet_packed": (C.c_int32, [_vp, _vp, _i64p, C.POINTER(C.c_int32)]),
     "lda_max_doc_length": (C.c_int32, [_vp, C.POINTER(C.c_int32)]),
     "lda_doc_topic_histograms": (C.c_int32, [_vp, C.c_int32, _i32p, _i32p]),

@@ -216,6 +216,11 @@ hipError_t dalloc(T** p, size_t n) {
   return hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T));
 }
 
+// lda_score_docs' chunks (the scratch bound stated in lda_mi355x.h): queries
+// per chunk, and fp64 scores per chunk (32 MiB)
+constexpr int64_t SCORE_QUERIES = 1024;
+constexpr int64_t SCORE_CELLS = int64_t(1) << 22;
+
 }  // namespace
 
 namespace lda_abi {
@@ -283,6 +288,11 @@ struct lda_ctx {
   int32_t *inf_words = nullptr, *inf_z = nullptr, *inf_acc = nullptr, *inf_q = nullptr;
   int64_t *inf_doff = nullptr, *inf_range = nullptr;
   size_t inf_cap[6] = {};
+  // lda_score_docs: grow-only scratch -- the query chunk's rows and constants
+  // [Qc (K + 2)], the document chunk's scores [Qc x Mc] and ids [Mc]
+  double *score_theta = nullptr, *score_out = nullptr;
+  int64_t* score_docs = nullptr;
+  size_t score_cap[3] = {};
   // 16-bit rows of the snapshot (LDA_SAMPLER_DENSE)
   uint16_t* nw16 = nullptr;
   uint8_t* wide = nullptr;
@@ -428,6 +438,7 @@ struct lda_ctx {
                     (void*)inv, (void*)inv_m1, (void*)partial, (void*)nonzero, (void*)ent,
                     (void*)row_off, (void*)row_nnz, (void*)row_rnd, (void*)nw16, (void*)wide, (void*)inf_words,
                     (void*)inf_z, (void*)inf_acc, (void*)inf_q, (void*)inf_doff, (void*)inf_range,
+                    (void*)score_theta, (void*)score_out, (void*)score_docs,
                     (void*)perm, (void*)items, (void*)warm.range_doc, (void*)steady.range_doc,
                     (void*)big.tab, (void*)big.tab_m1, (void*)big.F, (void*)big.pfx, (void*)big.scal})
       if (p) (void)hipFree(p);
@@ -2271,6 +2282,135 @@ lda_status lda_infer(lda_ctx* c, int64_t Dh, const int64_t* doc_off, const int32
       sum += v;
     }
     for (int k = 0; k < c->K; ++k) theta[(size_t)d * c->K + k] /= sum;
+  }
+  return LDA_OK;
+  });
+}
+
+lda_status lda_score_docs(lda_ctx* c, int32_t metric, int64_t Q, const double* theta, int64_t doc_begin, int64_t M,
+                          const int64_t* docs, double* scores) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (metric != LDA_SCORE_COSINE && metric != LDA_SCORE_MSE)
+    return fail(LDA_ERR_INVALID_ARG, "metric must be LDA_SCORE_COSINE or LDA_SCORE_MSE");
+  if (Q < 0 || M < 0) return fail(LDA_ERR_INVALID_ARG, "bad sizes");
+  if (c->pending) return fail(LDA_ERR_STATE, "scoring with a pending delta: call lda_apply first");
+  if (docs) {
+    if (doc_begin != 0) return fail(LDA_ERR_INVALID_ARG, "doc_begin must be 0 with a document list");
+    for (int64_t j = 0; j < M; ++j)
+      if (docs[j] < 0 || docs[j] >= c->D) return fail(LDA_ERR_INVALID_ARG, "document id out of range [0, D)");
+  } else if (doc_begin < 0 || doc_begin > c->D || M > c->D - doc_begin) {
+    return fail(LDA_ERR_INVALID_ARG, "document range out of [0, D)");
+  }
+  if (Q == 0 || M == 0) return LDA_OK;
+  if (!theta || !scores) return fail(LDA_ERR_INVALID_ARG, "null argument");
+  const int32_t K = c->K;
+  // the per-query constants in fp64: aq = alpha . theta_q, tq2 = |theta_q|^2
+  std::vector<double> qconst = host_vector<double>((size_t)Q * 2);
+  for (int64_t q = 0; q < Q; ++q) {
+    const double* row = theta + (size_t)q * K;
+    double sum = 0.0, aq = 0.0, tq2 = 0.0;
+    for (int k = 0; k < K; ++k) {
+      if (!(row[k] >= 0.0) || !std::isfinite(row[k]))
+        return fail(LDA_ERR_INVALID_ARG, "theta holds a negative or non-finite entry");
+      sum += row[k];
+      aq += c->alpha[(size_t)k] * row[k];
+      tq2 += row[k] * row[k];
+    }
+    if (!(sum > 0.0) || !(tq2 > 0.0) || !std::isfinite(tq2))
+      return fail(LDA_ERR_INVALID_ARG, "a theta row sums to zero (or its squared norm leaves fp64's range)");
+    qconst[(size_t)q * 2] = aq;
+    qconst[(size_t)q * 2 + 1] = tq2;
+  }
+  double a2 = 0.0, A = 0.0;
+  for (int k = 0; k < K; ++k) {
+    a2 += c->alpha[(size_t)k] * c->alpha[(size_t)k];
+    A += c->alpha[(size_t)k];
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  // chunks: SCORE_QUERIES queries x as many documents as SCORE_CELLS scores hold
+  const int64_t Qc = std::min<int64_t>(Q, SCORE_QUERIES);
+  const int64_t Mc = std::min<int64_t>(M, std::max<int64_t>(1, SCORE_CELLS / Qc));
+  hipError_t e = hipSuccess;
+  auto chk = [&](hipError_t x) {
+    if (e == hipSuccess) e = x;
+  };
+  auto need = [&](auto*& ptr, size_t n, int slot) {
+    if (e != hipSuccess || n <= c->score_cap[slot]) return;
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr;
+    c->score_cap[slot] = 0;
+    chk(dalloc(&ptr, n));
+    if (e == hipSuccess) c->score_cap[slot] = n;
+  };
+  // a chunk's queries travel as transposed register tiles [K x width] (rows
+  // past the last query zero), widths DOC_SCORE_TILE and, for a rest of at
+  // most DOC_SCORE_TILE_SMALL queries, DOC_SCORE_TILE_SMALL
+  auto tile_width = [](int64_t rem) {
+    return rem <= lda::DOC_SCORE_TILE_SMALL ? (int64_t)lda::DOC_SCORE_TILE_SMALL : (int64_t)lda::DOC_SCORE_TILE;
+  };
+  const size_t rows_cap = (size_t)((Qc + lda::DOC_SCORE_TILE - 1) / lda::DOC_SCORE_TILE * lda::DOC_SCORE_TILE) * K;
+  need(c->score_theta, rows_cap + (size_t)Qc * 2, 0);
+  need(c->score_out, (size_t)Qc * Mc, 1);
+  if (docs) need(c->score_docs, (size_t)Mc, 2);
+  HIP_TRY(e);
+  std::vector<double> stage = host_vector<double>(rows_cap + (size_t)Qc * 2);
+  const int wave_blocks = c->cus * 8;
+  for (int64_t q0 = 0; q0 < Q; q0 += Qc) {
+    const int64_t qn = std::min<int64_t>(Qc, Q - q0);
+    size_t rows = 0;
+    for (int64_t t0 = 0; t0 < qn;) {
+      const int64_t w = tile_width(qn - t0), nq = std::min(w, qn - t0);
+      double* tile = stage.data() + rows;
+      std::fill(tile, tile + (size_t)w * K, 0.0);
+      for (int64_t t = 0; t < nq; ++t)
+        for (int k = 0; k < K; ++k) tile[(size_t)k * w + t] = theta[(size_t)(q0 + t0 + t) * K + k];
+      rows += (size_t)w * K;
+      t0 += nq;
+    }
+    std::copy(qconst.begin() + (size_t)q0 * 2, qconst.begin() + (size_t)(q0 + qn) * 2, stage.begin() + rows);
+    const double* dq = c->score_theta + rows;   // the chunk's constants behind its tiles
+    HIP_TRY(hipMemcpyAsync(c->score_theta, stage.data(), sizeof(double) * (rows + (size_t)qn * 2),
+                           hipMemcpyHostToDevice, c->stream));
+    for (int64_t j0 = 0; j0 < M; j0 += Mc) {
+      const int64_t mn = std::min<int64_t>(Mc, M - j0);
+      if (docs)
+        HIP_TRY(hipMemcpyAsync(c->score_docs, docs + j0, sizeof(int64_t) * (size_t)mn, hipMemcpyHostToDevice,
+                               c->stream));
+      lda::DocScoreArgs a{};
+      a.z = c->z;
+      a.doc_off = c->doc_off;
+      a.docs = docs ? c->score_docs : nullptr;
+      a.doc_begin = doc_begin + j0;
+      a.M = mn;
+      a.alpha = c->alpha_d;
+      a.K = K;
+      a.Kp = c->Kp;
+      a.metric = metric;
+      a.a2 = a2;
+      a.A = A;
+      a.ldo = mn;
+      const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((mn + 3) / 4, wave_blocks));
+      size_t tile_at = 0;
+      for (int64_t t0 = 0; t0 < qn;) {
+        const int64_t w = tile_width(qn - t0), nq = std::min(w, qn - t0);
+        a.theta = c->score_theta + tile_at;
+        a.qconst = dq + (size_t)t0 * 2;
+        a.nq = (int32_t)nq;
+        a.out = c->score_out + (size_t)t0 * mn;
+        HIP_TRY(lda::launch_doc_scores(a, blocks, c->stream));
+        tile_at += (size_t)w * K;
+        t0 += nq;
+      }
+      // rows of mn scores into the caller's rows of M
+      double* dst = scores + (size_t)q0 * M + j0;
+      if (mn == M)
+        HIP_TRY(hipMemcpyAsync(dst, c->score_out, sizeof(double) * (size_t)qn * mn, hipMemcpyDeviceToHost, c->stream));
+      else
+        HIP_TRY(hipMemcpy2DAsync(dst, sizeof(double) * (size_t)M, c->score_out, sizeof(double) * (size_t)mn,
+                                 sizeof(double) * (size_t)mn, (size_t)qn, hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));   // the scratch is reused by the next chunk
+    }
   }
   return LDA_OK;
   });

@@ -223,6 +223,25 @@ hipError_t launch_ll_docs(const int32_t* z, const int64_t* doc_off, int64_t D, c
 hipError_t launch_ll_words(const int32_t* nw, int64_t V, int32_t K, int32_t Kp, double beta,
                            double* partial, unsigned long long* nonzero, int blocks,
                            hipStream_t st);
+// lda_score_docs (k_doc_scores): one register tile of nq <= DOC_SCORE_TILE
+// queries against M documents
+constexpr int DOC_SCORE_TILE = 16;
+constexpr int DOC_SCORE_TILE_SMALL = 4;   // the tile for nq <= 4
+struct DocScoreArgs {
+  const int32_t* z;
+  const int64_t* doc_off;
+  const int64_t* docs;      // [M] shard-local document ids, or null: doc_begin + j
+  int64_t doc_begin, M;
+  const double* alpha;      // [K]
+  const double* theta;      // [K * T] transposed tile, theta[k * T + t] (T the tile's width,
+                            // rows t >= nq zero), 16-byte aligned
+  const double* qconst;     // [2 nq]: alpha . theta_q, |theta_q|^2 per query of the tile
+  int32_t nq, K, Kp, metric;
+  double a2, A;             // sum alpha^2, sum alpha
+  double* out;              // out[t * ldo + j], t < nq, j < M
+  int64_t ldo;
+};
+hipError_t launch_doc_scores(const DocScoreArgs& a, int blocks, hipStream_t st);
 // range workers per block of the sampler kernel used for (C, sampler): 4
 // waves, 16 for the large-K sparse kernel (C >= 32), 8 for the half-wave
 // dense kernel (4 waves x 2 halves)

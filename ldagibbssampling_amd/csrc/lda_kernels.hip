@@ -3689,6 +3689,72 @@ __global__ __launch_bounds__(256) void k_ll_docs(const int32_t* __restrict__ z,
   if (threadIdx.x == 0) partial[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
 }
 
+// lda_score_docs: cosine similarity / mean squared difference between up to
+// T topic distributions theta_q (a register tile of queries) and the topic
+// distribution p_d = (c + alpha) / (n_d + A) of every listed document
+// (getTopicProbabilities).  One wave per document, the document's counts in
+// the per-wave LDS histogram of k_ll_docs, read back through the document's
+// own tokens (the first lane to take topic k holds its count c), so a
+// document costs O(its tokens).  With a2 = sum alpha^2, aq = alpha . theta_q,
+// tq2 = |theta_q|^2 from the host:
+//   dot = sum_k c_k theta_q[k] + aq                     = (n_d + A) p_d . theta_q
+//   n2  = sum_{c_k > 0} c_k (c_k + 2 alpha_k) + a2      = (n_d + A)^2 |p_d|^2
+// Every sum is a fixed-order fp64 wave reduction (no floating-point atomics).
+// The tile's rows arrive transposed, theta[k * T + t] (rows past nq zero), so a
+// token gathers its topic's T values as one contiguous run of 16-byte loads.
+template <int T>
+__global__ __launch_bounds__(256) void k_doc_scores(const DocScoreArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int32_t h[];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  int32_t* hist = h + wid * a.Kp;
+  for (int i = lane; i < a.Kp; i += 64) hist[i] = 0;
+  wave_lds_fence();
+  const int32_t* __restrict__ z = a.z;
+  const double* __restrict__ alpha = a.alpha;
+  const double2* __restrict__ theta = reinterpret_cast<const double2*>(a.theta);
+  for (int64_t j = (int64_t)blockIdx.x * 4 + wid; j < a.M; j += (int64_t)gridDim.x * 4) {
+    const int64_t d = a.docs ? a.docs[j] : a.doc_begin + j;
+    const int64_t t0 = a.doc_off[d], t1 = a.doc_off[d + 1];
+    for (int64_t i = t0 + lane; i < t1; i += 64) atomicAdd(&hist[z[i]], 1);
+    wave_lds_fence();
+    double n2 = 0.0, dot[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) dot[t] = 0.0;
+    // every topic of the document is taken by exactly one lane, which also
+    // leaves its cell zero for the next document
+    for (int64_t i = t0 + lane; i < t1; i += 64) {
+      const int k = z[i];
+      const int32_t c = atomicExch(&hist[k], 0);
+      if (c > 0) {
+        const double cd = (double)c;
+        n2 += cd * (cd + 2.0 * alpha[k]);
+        const double2* row = theta + (size_t)k * (T / 2);
+#pragma unroll
+        for (int t = 0; t < T / 2; ++t) {
+          const double2 v = row[t];
+          dot[2 * t] += cd * v.x;
+          dot[2 * t + 1] += cd * v.y;
+        }
+      }
+    }
+    wave_lds_fence();
+    n2 = wave_sum_d(n2) + a.a2;
+#pragma unroll
+    for (int t = 0; t < T; ++t) dot[t] = wave_sum_d(dot[t]);
+    if (lane == 0) {
+      const double S = (double)(t1 - t0) + a.A;
+#pragma unroll
+      for (int t = 0; t < T; ++t) {
+        if (t < a.nq) {
+          const double dt = dot[t] + a.qconst[2 * t], tq2 = a.qconst[2 * t + 1];
+          a.out[(int64_t)t * a.ldo + j] = a.metric == 0 ? dt / (sqrt(n2) * sqrt(tq2))
+                                                        : (n2 / (S * S) - 2.0 * dt / S + tq2) / (double)a.K;
+        }
+      }
+    }
+  }
+}
+
 // Word part: sum over nonzero nw cells of logGammaStirling(beta + count).
 __global__ __launch_bounds__(256) void k_ll_words(const int32_t* __restrict__ nw, int64_t V,
                                                   int32_t K, int32_t Kp, double beta,
@@ -4411,6 +4477,17 @@ hipError_t launch_ll_docs(const int32_t* z, const int64_t* doc_off, int64_t D, c
                           hipStream_t st) {
   hipLaunchKernelGGL(k_ll_docs, dim3(blocks), dim3(256), 4 * Kp * sizeof(int32_t), st, z, doc_off, D,
                      alpha, alpha_sum, K, Kp, partial);
+  return hipGetLastError();
+}
+
+hipError_t launch_doc_scores(const DocScoreArgs& a, int blocks, hipStream_t st) {
+  if (a.M <= 0 || a.nq <= 0) return hipSuccess;
+  if (a.nq > DOC_SCORE_TILE) return hipErrorInvalidValue;
+  const size_t lds = 4 * (size_t)a.Kp * sizeof(int32_t);   // 64 KB at Kp = 4096: the default limit
+  if (a.nq <= DOC_SCORE_TILE_SMALL)
+    hipLaunchKernelGGL(k_doc_scores<DOC_SCORE_TILE_SMALL>, dim3(blocks), dim3(256), lds, st, a);
+  else
+    hipLaunchKernelGGL(k_doc_scores<DOC_SCORE_TILE>, dim3(blocks), dim3(256), lds, st, a);
   return hipGetLastError();
 }
 

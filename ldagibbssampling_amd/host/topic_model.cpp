@@ -28,6 +28,7 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <numeric>
 #include <sstream>
 
@@ -1187,6 +1188,98 @@ void ParallelTopicModel::infer(int64_t Dh, const int64_t* doc_off, const int32_t
         "lda_infer");
 }
 
+void ParallelTopicModel::scoreTheta(int32_t metric, int64_t Q, const double* theta, int64_t M, const int64_t* docs,
+                                    double* scores) {
+  ensureShards();
+  const int64_t D = numDocs();
+  if (Q < 0 || M < 0) raise(LDA_ERR_INVALID_ARG, "bad sizes");
+  if (M == 0) return;
+  if (!docs && M != D) raise(LDA_ERR_INVALID_ARG, "without a document list M must be the number of documents");
+  for (int64_t j = 0; docs && j < M; ++j)
+    if (docs[j] < 0 || docs[j] >= D) raise(LDA_ERR_INVALID_ARG, "document id out of range [0, D)");
+  if (Q == 0 || M == 0) return;
+  if (!theta || !scores) raise(LDA_ERR_INVALID_ARG, "null argument");
+  const std::vector<int64_t>& begin = shards_->doc_begin;
+  const size_t G = shards_->ctx.size();
+  std::vector<double> part;
+  if (!docs) {
+    for (size_t g = 0; g < G; ++g) {
+      const int64_t d0 = begin[g], m = begin[g + 1] - d0;
+      if (m == 0) continue;
+      if (G == 1) {
+        check(lda_score_docs(shards_->ctx[g], metric, Q, theta, 0, m, nullptr, scores), "lda_score_docs");
+        return;
+      }
+      part.resize((size_t)Q * m);
+      check(lda_score_docs(shards_->ctx[g], metric, Q, theta, 0, m, nullptr, part.data()), "lda_score_docs");
+      for (int64_t q = 0; q < Q; ++q)
+        std::copy(part.begin() + q * m, part.begin() + (q + 1) * m, scores + q * M + d0);
+    }
+    return;
+  }
+  // the list's documents by shard (shard-local ids), and where each goes in
+  // the caller's order
+  std::vector<std::vector<int64_t>> local(G), pos(G);
+  for (int64_t j = 0; j < M; ++j) {
+    const size_t g = (size_t)(std::upper_bound(begin.begin(), begin.end(), docs[j]) - begin.begin()) - 1;
+    local[g].push_back(docs[j] - begin[g]);
+    pos[g].push_back(j);
+  }
+  for (size_t g = 0; g < G; ++g) {
+    const int64_t m = (int64_t)local[g].size();
+    if (m == 0) continue;
+    part.resize((size_t)Q * m);
+    check(lda_score_docs(shards_->ctx[g], metric, Q, theta, 0, m, local[g].data(), part.data()), "lda_score_docs");
+    for (int64_t q = 0; q < Q; ++q)
+      for (int64_t i = 0; i < m; ++i) scores[q * M + pos[g][(size_t)i]] = part[(size_t)(q * m + i)];
+  }
+}
+
+void ParallelTopicModel::scoreTop(int32_t metric, int64_t Q, const double* theta, int32_t n, int64_t* doc_ids,
+                                  double* scores) {
+  ensureShards();
+  if (Q < 0 || n < 0) raise(LDA_ERR_INVALID_ARG, "bad sizes");
+  if (metric != LDA_SCORE_COSINE && metric != LDA_SCORE_MSE)
+    raise(LDA_ERR_INVALID_ARG, "metric must be LDA_SCORE_COSINE or LDA_SCORE_MSE");
+  if (Q == 0 || n == 0) return;
+  if (!theta || !doc_ids || !scores) raise(LDA_ERR_INVALID_ARG, "null argument");
+  using Hit = std::pair<double, int64_t>;   // (score, global document id)
+  const bool largest = metric == LDA_SCORE_COSINE;
+  auto better = [largest](const Hit& a, const Hit& b) {
+    if (a.first != b.first) return largest ? a.first > b.first : a.first < b.first;
+    return a.second < b.second;
+  };
+  std::vector<std::vector<Hit>> best((size_t)Q);
+  // chunks of at most 2^22 scores on the host, shard by shard
+  const int64_t chunk = std::max<int64_t>(1, (int64_t(1) << 22) / Q);
+  std::vector<double> part;
+  for (size_t g = 0; g < shards_->ctx.size(); ++g) {
+    const int64_t d0 = shards_->doc_begin[g], Dg = shards_->doc_begin[g + 1] - d0;
+    for (int64_t j0 = 0; j0 < Dg; j0 += chunk) {
+      const int64_t m = std::min(chunk, Dg - j0);
+      part.resize((size_t)Q * m);
+      check(lda_score_docs(shards_->ctx[g], metric, Q, theta, j0, m, nullptr, part.data()), "lda_score_docs");
+      for (int64_t q = 0; q < Q; ++q) {
+        std::vector<Hit>& b = best[(size_t)q];
+        for (int64_t i = 0; i < m; ++i) b.emplace_back(part[(size_t)(q * m + i)], d0 + j0 + i);
+        if ((int64_t)b.size() > n) {
+          std::nth_element(b.begin(), b.begin() + n, b.end(), better);
+          b.resize((size_t)n);
+        }
+      }
+    }
+  }
+  for (int64_t q = 0; q < Q; ++q) {
+    std::vector<Hit>& b = best[(size_t)q];
+    std::sort(b.begin(), b.end(), better);
+    for (int64_t i = 0; i < n; ++i) {
+      const bool have = i < (int64_t)b.size();
+      doc_ids[q * n + i] = have ? b[(size_t)i].second : -1;
+      scores[q * n + i] = have ? b[(size_t)i].first : std::numeric_limits<double>::quiet_NaN();
+    }
+  }
+}
+
 }  // namespace lda_host
 
 // ------------------------------------------------------------------ C ABI
@@ -1497,6 +1590,46 @@ lda_status ldatm_infer(ldatm* m, int64_t Dh, const int64_t* doc_off, const int32
                        double* theta) {
   TM_CHECK(m);
   return guard([&] { m->model.infer(Dh, doc_off, words, num_iterations, thinning, burn_in, seed, theta); });
+}
+
+lda_status ldatm_score_theta(ldatm* m, int32_t metric, int64_t Q, const double* theta, int64_t M,
+                             const int64_t* docs, double* scores) {
+  TM_CHECK(m);
+  if (!scores) {
+    g_tm_error = "null scores";
+    return LDA_ERR_INVALID_ARG;
+  }
+  return guard([&] { m->model.scoreTheta(metric, Q, theta, M, docs, scores); });
+}
+
+lda_status ldatm_score(ldatm* m, int32_t metric, int64_t Dh, const int64_t* doc_off, const int32_t* words,
+                       int32_t num_iterations, int32_t thinning, int32_t burn_in, uint64_t seed, int64_t M,
+                       const int64_t* docs, double* scores, double* theta_out) {
+  TM_CHECK(m);
+  if (!scores) {
+    g_tm_error = "null scores";
+    return LDA_ERR_INVALID_ARG;
+  }
+  return guard([&] {
+    std::vector<double> own;
+    double* theta = theta_out;
+    if (!theta && Dh > 0) {
+      own.resize((size_t)Dh * (size_t)m->model.numTopics());
+      theta = own.data();
+    }
+    m->model.infer(Dh, doc_off, words, num_iterations, thinning, burn_in, seed, theta);
+    m->model.scoreTheta(metric, Dh, theta, M, docs, scores);
+  });
+}
+
+lda_status ldatm_score_top(ldatm* m, int32_t metric, int64_t Q, const double* theta, int32_t n, int64_t* doc_ids,
+                           double* scores) {
+  TM_CHECK(m);
+  if (!doc_ids || !scores) {
+    g_tm_error = "null output";
+    return LDA_ERR_INVALID_ARG;
+  }
+  return guard([&] { m->model.scoreTop(metric, Q, theta, n, doc_ids, scores); });
 }
 
 }  // extern "C"

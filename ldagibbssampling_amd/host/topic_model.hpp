@@ -111,6 +111,17 @@ class ParallelTopicModel {
   void infer(int64_t Dh, const int64_t* doc_off, const int32_t* words, int32_t num_iterations,
              int32_t thinning, int32_t burn_in, uint64_t seed, double* theta);
 
+  // ---- prediction scoring (the reference's Predictor.predict /
+  //      scoresForChangelistOnTests, batched on the device: lda_score_docs) ----
+  // theta[Q*K] against the global document ids docs[M] (null: every document,
+  // M = numDocs()); scores[Q*M].  Each shard scores its own documents.
+  void scoreTheta(int32_t metric, int64_t Q, const double* theta, int64_t M, const int64_t* docs,
+                  double* scores);
+  // the n best documents per query, best first (cosine: largest; mse:
+  // smallest), ties by ascending id; doc_ids / scores [Q*n], entries past
+  // numDocs() are -1 / NaN
+  void scoreTop(int32_t metric, int64_t Q, const double* theta, int32_t n, int64_t* doc_ids, double* scores);
+
  private:
   void ensureShards();
   void markDirty();

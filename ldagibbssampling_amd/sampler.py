@@ -366,6 +366,26 @@ class GibbsSampler:
                                      int(burn_in), int(seed) & (2**64 - 1), theta), "lda_infer")
         return theta
 
+    def score_docs(self, theta, metric="cosine", docs=None, doc_begin: int = 0,
+                   num_docs: int | None = None) -> np.ndarray:
+        """lda_score_docs: similarity ("cosine" or "mse") of the rows of
+        theta[Q, K] to this shard's documents' topic distributions, computed on
+        the device from z.  docs: document ids (any order, duplicates allowed);
+        None: documents [doc_begin, doc_begin + num_docs) (default: to the
+        end).  Returns scores[Q, M] (fp64)."""
+        theta = capi.as_theta(theta, self.K)
+        m = capi.score_metric(metric)
+        if docs is not None:
+            ids = np.ascontiguousarray(docs, dtype=np.int64).reshape(-1)
+            M, begin, idp = len(ids), 0, (ids.ctypes.data if len(ids) else None)
+        else:
+            begin = int(doc_begin)
+            M, idp = (self.D - begin if num_docs is None else int(num_docs)), None
+        scores = np.zeros((len(theta), max(M, 0)), dtype=np.float64)
+        capi.check(self._L.lda_score_docs(self._h, m, len(theta), theta.ctypes.data, begin, M, idp,
+                                          scores.ctypes.data), "lda_score_docs")
+        return scores
+
     # ------------------------------------------- hyperparameter statistics
     def max_doc_length(self) -> int:
         m = C.c_int32()

@@ -80,6 +80,10 @@ TM_SIGNATURES = {
     "ldatm_save": (_i32, [_vp, C.c_char_p]),
     "ldatm_load": (_i32, [C.POINTER(_vp), C.c_char_p]),
     "ldatm_infer": (_i32, [_vp, C.c_int64, _i64p, _vp, _i32, _i32, _i32, C.c_uint64, _f64p]),
+    "ldatm_score_theta": (_i32, [_vp, _i32, C.c_int64, _vp, C.c_int64, _vp, _vp]),
+    "ldatm_score": (_i32, [_vp, _i32, C.c_int64, _vp, _vp, _i32, _i32, _i32, C.c_uint64, C.c_int64, _vp,
+                           _vp, _vp]),
+    "ldatm_score_top": (_i32, [_vp, _i32, C.c_int64, _vp, _i32, _vp, _vp]),
     "ldatm_format_double": (_i32, [C.c_double, _i32, C.c_char_p, C.c_size_t]),
     "ldatm_last_error": (C.c_char_p, []),
 }
@@ -427,6 +431,43 @@ class ParallelTopicModel:
     def getInferencer(self) -> "TopicInferencer":
         return TopicInferencer(self)
 
+    # ------------------------------------------------ prediction scoring
+    def scoreDistributions(self, theta, docs=None, metric="cosine") -> np.ndarray:
+        """Similarity ("cosine" or "mse") of the rows of theta[Q, K] to
+        getTopicProbabilities(d) of the training documents `docs` (global ids,
+        any order; None = all), computed on the device: scores[Q, M]."""
+        theta = capi.as_theta(theta, self.numTopics)
+        m = capi.score_metric(metric)
+        ids, M = _doc_ids(docs, self)
+        scores = np.zeros((len(theta), M), np.float64)
+        _check(self._L.ldatm_score_theta(self._h, m, len(theta), theta.ctypes.data, M,
+                                         ids.ctypes.data if ids is not None and M else None,
+                                         scores.ctypes.data), "scoreDistributions")
+        return scores
+
+    def topDocuments(self, theta, n: int, metric="cosine"):
+        """The n best training documents per row of theta[Q, K]: (doc_ids[Q, n],
+        scores[Q, n]), best first (largest cosine / smallest mse, ties by
+        ascending id); past the number of documents: id -1, score NaN."""
+        theta = capi.as_theta(theta, self.numTopics)
+        m = capi.score_metric(metric)
+        n = int(n)
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        ids = np.full((len(theta), n), -1, np.int64)
+        scores = np.full((len(theta), n), np.nan, np.float64)
+        _check(self._L.ldatm_score_top(self._h, m, len(theta), theta.ctypes.data, n, ids.ctypes.data,
+                                       scores.ctypes.data), "topDocuments")
+        return ids, scores
+
+
+def _doc_ids(docs, model):
+    """(int64 ids or None, M) of a scoring call's document list."""
+    if docs is None:
+        return None, model._shape()[2]
+    ids = np.ascontiguousarray(docs, dtype=np.int64).reshape(-1)
+    return ids, len(ids)
+
 
 class TopicInferencer:
     """getSampledDistribution against the model's current (frozen) counts."""
@@ -443,6 +484,24 @@ class TopicInferencer:
                                          int(thinning), int(burnIn), int(seed) & (2**64 - 1), theta),
                "getSampledDistribution")
         return theta
+
+    def scoreInstances(self, instances, numIterations: int = 100, thinning: int = 10,
+                       burnIn: int = 10, seed: int = 0, docs=None, metric="cosine"):
+        """getSampledDistributions of `instances`, then their similarity to the
+        training documents `docs` (None = all) as scoreDistributions, in one
+        native call: (scores[Q, M], theta[Q, K])."""
+        m = capi.score_metric(metric)
+        off, w = _flatten(list(instances))
+        ids, M = _doc_ids(docs, self.model)
+        Q = len(off) - 1
+        theta = np.zeros((Q, self.model.numTopics), np.float64)
+        scores = np.zeros((Q, M), np.float64)
+        _check(self.model._L.ldatm_score(self.model._h, m, Q, off.ctypes.data, w.ctypes.data if len(w) else None,
+                                         int(numIterations), int(thinning), int(burnIn),
+                                         int(seed) & (2**64 - 1), M,
+                                         ids.ctypes.data if ids is not None and M else None,
+                                         scores.ctypes.data, theta.ctypes.data), "scoreInstances")
+        return scores, theta
 
     def getSampledDistribution(self, instance, numIterations: int = 100, thinning: int = 10,
                                burnIn: int = 10, seed: int = 0) -> np.ndarray:
