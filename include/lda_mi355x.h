@@ -392,6 +392,44 @@ lda_status lda_infer(lda_ctx* ctx, int64_t Dh, const int64_t* doc_off, const int
 lda_status lda_score_docs(lda_ctx* ctx, int32_t metric, int64_t Q, const double* theta,
                           int64_t doc_begin, int64_t M, const int64_t* docs, double* scores);
 
+/* Held-out log likelihood by document completion, on the device against the
+ * global counts this shard holds (the int32 nw rows and nwsum): for held-out
+ * document d with topic distribution theta_d (a row of theta[Dh*K]; any
+ * non-negative row, it need not sum to 1) and scored tokens
+ * words[doc_off[d] - doc_off[0] .. doc_off[d+1] - doc_off[0]),
+ *     doc_ll[d] = sum_i log sum_k theta_d[k] (nw[w_i,k] + beta) / (nwsum[k] + V beta)
+ * in fp64.  Every token is scored, also one whose type has no training
+ * tokens (its term is beta sum_k theta_d[k] / (nwsum[k] + V beta) > 0).  An
+ * empty document gives 0.0.  total (may be NULL) receives doc_ll[0] + ... +
+ * doc_ll[Dh-1] added in that order on the host, so it equals the caller's own
+ * sum exactly.  The sums are fixed-order reductions without floating-point
+ * atomics: a call repeats bit for bit, and doc_ll[d] depends on document d's
+ * theta row and tokens alone, not on Dh, the other documents or the chunks.
+ * Errors: LDA_ERR_STATE with a pending delta (call lda_apply first);
+ * LDA_ERR_INVALID_ARG for a NULL ctx, theta, doc_off or doc_ll (words may be
+ * NULL only without tokens), Dh < 0, a doc_off that is not monotone, a word id
+ * outside [0, V), a theta entry that is negative or not finite, or a theta
+ * row that sums to zero.  Dh = 0 succeeds and touches nothing.
+ * Device scratch is grow-only and kept by the context.  The documents are cut
+ * into chunks of at most max(1, 2^22 / K) documents (1024 at K = 4096) and at
+ * most 2^23 tokens (a single longer document is a chunk of its own), so the
+ * scratch never exceeds 32 MiB of theta + 32 MiB of word ids (or 4 bytes per
+ * token of the longest document, if that is more) + 16 bytes per document of
+ * a chunk for offsets and results (<= 64 MiB at K = 1) + 8 Kp bytes, whatever
+ * Dh is.  Waits for the context's stream. */
+lda_status lda_heldout_loglik(lda_ctx* ctx, int64_t Dh, const double* theta, const int64_t* doc_off,
+                              const int32_t* words, double* doc_ll, double* total);
+/* Document completion in one call: lda_infer on the observed halves
+ * (obs_off, obs_words and the four sampling arguments exactly as lda_infer
+ * takes them), then lda_heldout_loglik of the inferred distributions on the
+ * scored halves (sc_off, sc_words).  theta_out[Dh*K] (may be NULL) receives
+ * what lda_infer returns for the same arguments, bit for bit.  Errors as the
+ * two calls; the scored halves are checked before the inference runs. */
+lda_status lda_doc_completion(lda_ctx* ctx, int64_t Dh, const int64_t* obs_off, const int32_t* obs_words,
+                              const int64_t* sc_off, const int32_t* sc_words, int32_t num_iterations,
+                              int32_t thinning, int32_t burn_in, uint64_t seed, double* doc_ll,
+                              double* total, double* theta_out);
+
 /* Mallet-layout adapter: typeTopicCounts as packed (count << topic_bits) |
  * topic rows sorted descending, rows[row_off[w] .. row_off[w+1]) with
  * row_off[V+1]; row length = min(K, typeTotal[w]) exactly as Mallet allocates
@@ -496,7 +534,9 @@ void lda_debug_fail_host_alloc(int32_t nth);
  * large-K sampler's draw (C >= 32: exact fixed-point doc part, own-entry
  * accept / re-draw), sequential sweeps recount under LDA_COUNT_RECOUNT,
  * lda_exchange_unpack_lists, lda_counts_checksum; 7 -- lda_set_exchange_cells
- * (four 8-bit cells per packed word); 8 -- lda_score_docs. */
+ * (four 8-bit cells per packed word); 8 -- lda_score_docs.
+ * lda_heldout_loglik and lda_doc_completion came later and only add symbols,
+ * so the version stays 8. */
 #define LDA_ABI_VERSION 8
 const char* lda_version(void);
 int32_t lda_abi_version(void);

@@ -18,6 +18,9 @@
  *   getInferencer().getSampledDistribution(...)   -> ldatm_infer
  *   the predict loop's similarity to every
  *   training document (Predictor.predict)        -> ldatm_score / ldatm_score_theta / ldatm_score_top
+ *   held-out log likelihood / perplexity by
+ *   document completion, and its trace
+ *   during estimate()                            -> ldatm_evaluate / ldatm_heldout_loglik / ldatm_set_held_out
  * Word ids index the model's alphabet (Mallet's Alphabet: insertion order).
  * Errors: lda_status codes of lda_mi355x.h, message in ldatm_last_error().
  */
@@ -207,6 +210,47 @@ lda_status ldatm_score(ldatm* m, int32_t metric, int64_t Dh, const int64_t* doc_
  * Errors as ldatm_score_theta (NULL doc_ids / scores, n < 0: INVALID_ARG). */
 lda_status ldatm_score_top(ldatm* m, int32_t metric, int64_t Q, const double* theta, int32_t n,
                            int64_t* doc_ids, double* scores);
+
+/* Held-out evaluation by document completion, on the device (lda_heldout_loglik
+ * / lda_doc_completion of lda_mi355x.h; formulas and error bound there and in
+ * DESIGN 9c).  Both calls run on shard 0: every shard holds the same global
+ * counts, and the inference draws are keyed by a token's index in the batch,
+ * so spreading the documents over shards would change theta.  The results do
+ * not depend on the number of shards, bit for bit.
+ *
+ * ldatm_heldout_loglik: theta[Dh*K] and the scored tokens are given (word ids
+ * must lie in [0, V)); doc_ll[Dh], and total (may be NULL) = their sum added
+ * in document order.  Errors as lda_heldout_loglik. */
+lda_status ldatm_heldout_loglik(ldatm* m, int64_t Dh, const double* theta, const int64_t* doc_off,
+                                const int32_t* words, double* doc_ll, double* total);
+/* ldatm_evaluate: whole held-out documents are given.  Tokens outside [0, V)
+ * are dropped, as ldatm_infer drops them, and are not counted; then the
+ * first floor(L/2) tokens of each document are observed (ldatm_infer's
+ * arguments apply to them) and the rest are scored.  doc_ll[Dh]; total,
+ * tokens_scored (the number of scored tokens: perplexity =
+ * exp(-total / tokens_scored)) and theta_out[Dh*K] may be NULL. */
+lda_status ldatm_evaluate(ldatm* m, int64_t Dh, const int64_t* doc_off, const int32_t* words,
+                          int32_t num_iterations, int32_t thinning, int32_t burn_in, uint64_t seed,
+                          double* doc_ll, double* total, int64_t* tokens_scored, double* theta_out);
+/* The split ldatm_evaluate makes (host-only): obs_off / sc_off [Dh+1];
+ * obs_words / sc_words (may be NULL to get the offsets only) need room for
+ * the document's tokens. */
+lda_status ldatm_completion_split(int32_t num_types, int64_t Dh, const int64_t* doc_off, const int32_t* words,
+                                  int64_t* obs_off, int32_t* obs_words, int64_t* sc_off, int32_t* sc_words);
+/* A held-out set that ldatm_estimate evaluates (as ldatm_evaluate, with these
+ * arguments) after every sweep `it` with it % interval == 0, after that
+ * sweep's alpha / beta optimisation: it logs "<it> held-out LL/token: x" and
+ * appends (it, total / tokens_scored) to the trace, which ldatm_estimate
+ * clears when it starts.  interval = 0 turns it off.  The evaluation reads the
+ * counts and writes only its own scratch: z, alpha and beta after
+ * ldatm_estimate are the same bits with it on or off.  The documents are
+ * copied.  The held-out set is not written by ldatm_save (the checkpoint
+ * format is unchanged): set it again after ldatm_load. */
+lda_status ldatm_set_held_out(ldatm* m, int64_t Dh, const int64_t* doc_off, const int32_t* words,
+                              int32_t interval, int32_t num_iterations, int32_t thinning, int32_t burn_in,
+                              uint64_t seed);
+/* shaped like ldatm_get_ll_trace */
+lda_status ldatm_get_held_out_trace(ldatm* m, int32_t* iterations, double* ll, int32_t cap, int32_t* n);
 
 /* The number renderings of Mallet's text outputs (host-only): style 0 =
  * Double.toString (printDocumentTopics weights), 1 = NumberFormat with at

@@ -18,7 +18,7 @@ def __getattr__(name):
     if name == "GibbsSampler":
         from .sampler import GibbsSampler
         return GibbsSampler
-    if name in ("ParallelTopicModel", "TopicInferencer", "InstanceList"):
+    if name in ("ParallelTopicModel", "TopicInferencer", "InstanceList", "HeldOutEvaluator"):
         from . import topic_model
         return getattr(topic_model, name)
     raise AttributeError(name)

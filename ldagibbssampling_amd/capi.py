@@ -54,6 +54,27 @@ def as_theta(theta, K: int) -> np.ndarray:
     return np.ascontiguousarray(t)
 
 
+def doc_completion_batch(C: int) -> int:
+    """Tokens per batch of k_doc_completion for Kp = 64 C (lda_kernels.h
+    doc_completion_batch): the document lengths around it are edge cases."""
+    return 64 if C <= 8 else 16
+
+
+def as_docs(doc_off, words, num_docs: int | None = None, what: str = "doc_off"):
+    """(int64 doc_off[Dh + 1], int32 words) of a batch of documents as
+    C-contiguous arrays; offsets that do not fit the words (or the expected
+    number of documents) are refused before any native call."""
+    off = np.ascontiguousarray(doc_off, dtype=np.int64).reshape(-1)
+    w = np.ascontiguousarray(words, dtype=np.int32).reshape(-1)
+    if len(off) < 1:
+        raise ValueError(f"{what} must hold at least one offset")
+    if num_docs is not None and len(off) != num_docs + 1:
+        raise ValueError(f"{what} must have {num_docs + 1} entries, not {len(off)}")
+    if int(off[-1]) - int(off[0]) != len(w):
+        raise ValueError(f"{what} spans {int(off[-1]) - int(off[0])} tokens but words holds {len(w)}")
+    return off, w
+
+
 class LdaError(RuntimeError):
     def __init__(self, status: int, where: str, message: str):
         self.status = status
@@ -112,6 +133,9 @@ SIGNATURES = {
     "lda_infer": (C.c_int32, [_vp, C.c_int64, _i64p, _i32p, C.c_int32, C.c_int32, C.c_int32,
                               C.c_uint64, _f64p]),
     "lda_score_docs": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, C.c_int64, C.c_int64, _vp, _vp]),
+    "lda_heldout_loglik": (C.c_int32, [_vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "lda_doc_completion": (C.c_int32, [_vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_uint64, _vp, _vp, _vp]),
     "lda_to_mallet_packed": (C.c_int32, [_vp, _vp, _i64p, C.POINTER(C.c_int32)]),
     "lda_max_doc_length": (C.c_int32, [_vp, C.POINTER(C.c_int32)]),
     "lda_doc_topic_histograms": (C.c_int32, [_vp, C.c_int32, _i32p, _i32p]),

@@ -220,6 +220,10 @@ hipError_t dalloc(T** p, size_t n) {
 // per chunk, and fp64 scores per chunk (32 MiB)
 constexpr int64_t SCORE_QUERIES = 1024;
 constexpr int64_t SCORE_CELLS = int64_t(1) << 22;
+// lda_heldout_loglik's chunks: fp64 theta entries per chunk (32 MiB) and
+// tokens per chunk (32 MiB of ids; a single longer document goes alone)
+constexpr int64_t HELDOUT_THETA_CELLS = int64_t(1) << 22;
+constexpr int64_t HELDOUT_TOKENS = int64_t(1) << 23;
 
 }  // namespace
 
@@ -293,6 +297,12 @@ struct lda_ctx {
   double *score_theta = nullptr, *score_out = nullptr;
   int64_t* score_docs = nullptr;
   size_t score_cap[3] = {};
+  // lda_heldout_loglik: grow-only scratch -- the chunk's theta rows [Dc x K],
+  // its results [Dc], inv [Kp], its token ids and its offsets [Dc + 1]
+  double *held_theta = nullptr, *held_ll = nullptr, *held_inv = nullptr;
+  int32_t* held_words = nullptr;
+  int64_t* held_off = nullptr;
+  size_t held_cap[5] = {};
   // 16-bit rows of the snapshot (LDA_SAMPLER_DENSE)
   uint16_t* nw16 = nullptr;
   uint8_t* wide = nullptr;
@@ -439,6 +449,7 @@ struct lda_ctx {
                     (void*)row_off, (void*)row_nnz, (void*)row_rnd, (void*)nw16, (void*)wide, (void*)inf_words,
                     (void*)inf_z, (void*)inf_acc, (void*)inf_q, (void*)inf_doff, (void*)inf_range,
                     (void*)score_theta, (void*)score_out, (void*)score_docs,
+                    (void*)held_theta, (void*)held_ll, (void*)held_inv, (void*)held_words, (void*)held_off,
                     (void*)perm, (void*)items, (void*)warm.range_doc, (void*)steady.range_doc,
                     (void*)big.tab, (void*)big.tab_m1, (void*)big.F, (void*)big.pfx, (void*)big.scal})
       if (p) (void)hipFree(p);
@@ -2413,6 +2424,138 @@ lda_status lda_score_docs(lda_ctx* c, int32_t metric, int64_t Q, const double* t
     }
   }
   return LDA_OK;
+  });
+}
+
+namespace {
+
+// the documents of a held-out call: monotone offsets, ids in [0, V)
+lda_status check_heldout_docs(const lda_ctx* c, int64_t Dh, const int64_t* doc_off, const int32_t* words) {
+  for (int64_t d = 1; d <= Dh; ++d)
+    if (doc_off[d] < doc_off[d - 1]) return fail(LDA_ERR_INVALID_ARG, "doc_off not monotone");
+  const int64_t N = doc_off[Dh] - doc_off[0];
+  if (N > 0 && !words) return fail(LDA_ERR_INVALID_ARG, "words is null");
+  for (int64_t i = 0; i < N; ++i)
+    if (words[i] < 0 || words[i] >= c->V) return fail(LDA_ERR_INVALID_ARG, "word id out of range [0, V)");
+  return LDA_OK;
+}
+
+}  // namespace
+
+lda_status lda_heldout_loglik(lda_ctx* c, int64_t Dh, const double* theta, const int64_t* doc_off,
+                              const int32_t* words_in, double* doc_ll, double* total) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (Dh < 0) return fail(LDA_ERR_INVALID_ARG, "bad sizes");
+  if (c->pending) return fail(LDA_ERR_STATE, "held-out likelihood with a pending delta: call lda_apply first");
+  if (Dh == 0) return LDA_OK;
+  if (!theta || !doc_off || !doc_ll) return fail(LDA_ERR_INVALID_ARG, "null argument");
+  if (lda_status s = check_heldout_docs(c, Dh, doc_off, words_in); s != LDA_OK) return s;
+  const int32_t K = c->K;
+  for (int64_t d = 0; d < Dh; ++d) {
+    const double* row = theta + (size_t)d * K;
+    double sum = 0.0;
+    for (int k = 0; k < K; ++k) {
+      if (!(row[k] >= 0.0) || !std::isfinite(row[k]))
+        return fail(LDA_ERR_INVALID_ARG, "theta holds a negative or non-finite entry");
+      sum += row[k];
+    }
+    if (!(sum > 0.0)) return fail(LDA_ERR_INVALID_ARG, "a theta row sums to zero");
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  const int32_t* words = words_in;
+  const int64_t first = doc_off[0];
+  // chunks of documents: at most HELDOUT_THETA_CELLS theta entries and
+  // HELDOUT_TOKENS tokens each (a single longer document goes alone)
+  const int64_t Dc = std::min<int64_t>(Dh, std::max<int64_t>(1, HELDOUT_THETA_CELLS / K));
+  std::vector<int64_t> cut(1, 0);
+  int64_t max_tokens = 1;
+  for (int64_t d0 = 0; d0 < Dh;) {
+    int64_t d1 = d0 + 1;
+    while (d1 < Dh && d1 - d0 < Dc && doc_off[d1 + 1] - doc_off[d0] <= HELDOUT_TOKENS) ++d1;
+    max_tokens = std::max(max_tokens, doc_off[d1] - doc_off[d0]);
+    cut.push_back(d1);
+    d0 = d1;
+  }
+  hipError_t e = hipSuccess;
+  auto chk = [&](hipError_t x) {
+    if (e == hipSuccess) e = x;
+  };
+  auto need = [&](auto*& ptr, size_t n, int slot) {
+    if (e != hipSuccess || n <= c->held_cap[slot]) return;
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr;
+    c->held_cap[slot] = 0;
+    chk(dalloc(&ptr, n));
+    if (e == hipSuccess) c->held_cap[slot] = n;
+  };
+  need(c->held_theta, (size_t)Dc * K, 0);
+  need(c->held_ll, (size_t)Dc, 1);
+  need(c->held_inv, (size_t)c->Kp, 2);
+  need(c->held_words, (size_t)max_tokens, 3);
+  need(c->held_off, (size_t)Dc + 1, 4);
+  HIP_TRY(e);
+  HIP_TRY(lda::launch_heldout_inv(c->nwsum, (double)c->V * c->beta, K, c->Kp, c->held_inv, c->stream));
+  std::vector<int64_t> off = host_vector<int64_t>((size_t)Dc + 1);
+  const int wave_blocks = c->cus * 8;
+  for (size_t ch = 0; ch + 1 < cut.size(); ++ch) {
+    const int64_t d0 = cut[ch], dn = cut[ch + 1] - d0;
+    const int64_t w0 = doc_off[d0], wn = doc_off[d0 + dn] - w0;
+    for (int64_t d = 0; d <= dn; ++d) off[(size_t)d] = doc_off[d0 + d] - w0;
+    HIP_TRY(hipMemcpyAsync(c->held_theta, theta + (size_t)d0 * K, sizeof(double) * (size_t)dn * K,
+                           hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->held_off, off.data(), sizeof(int64_t) * (size_t)(dn + 1), hipMemcpyHostToDevice,
+                           c->stream));
+    if (wn > 0)
+      HIP_TRY(hipMemcpyAsync(c->held_words, words + (w0 - first), sizeof(int32_t) * (size_t)wn,
+                             hipMemcpyHostToDevice, c->stream));
+    lda::DocCompletionArgs a{};
+    a.nw = c->nw;
+    a.inv = c->held_inv;
+    a.theta = c->held_theta;
+    a.doc_off = c->held_off;
+    a.words = c->held_words;
+    a.out = c->held_ll;
+    a.Dh = dn;
+    a.K = K;
+    a.Kp = c->Kp;
+    a.beta = c->beta;
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((dn + 3) / 4, wave_blocks));
+    HIP_TRY(lda::launch_doc_completion(a, blocks, c->stream));
+    HIP_TRY(hipMemcpyAsync(doc_ll + d0, c->held_ll, sizeof(double) * (size_t)dn, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));   // the scratch (and off) is reused by the next chunk
+  }
+  if (total) {
+    double t = 0.0;
+    for (int64_t d = 0; d < Dh; ++d) t += doc_ll[d];
+    *total = t;
+  }
+  return LDA_OK;
+  });
+}
+
+lda_status lda_doc_completion(lda_ctx* c, int64_t Dh, const int64_t* obs_off, const int32_t* obs_words,
+                              const int64_t* sc_off, const int32_t* sc_words, int32_t num_iterations,
+                              int32_t thinning, int32_t burn_in, uint64_t seed, double* doc_ll, double* total,
+                              double* theta_out) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (Dh < 0) return fail(LDA_ERR_INVALID_ARG, "bad sizes");
+  if (c->pending) return fail(LDA_ERR_STATE, "document completion with a pending delta: call lda_apply first");
+  if (Dh == 0) return LDA_OK;
+  if (!obs_off || !sc_off || !doc_ll) return fail(LDA_ERR_INVALID_ARG, "null argument");
+  // the scored halves are checked before the inference runs
+  if (lda_status s = check_heldout_docs(c, Dh, sc_off, sc_words); s != LDA_OK) return s;
+  std::vector<double> own;
+  double* theta = theta_out;
+  if (!theta) {
+    own = host_vector<double>((size_t)Dh * c->K);
+    theta = own.data();
+  }
+  if (lda_status s = lda_infer(c, Dh, obs_off, obs_words, num_iterations, thinning, burn_in, seed, theta);
+      s != LDA_OK)
+    return s;
+  return lda_heldout_loglik(c, Dh, theta, sc_off, sc_words, doc_ll, total);
   });
 }
 

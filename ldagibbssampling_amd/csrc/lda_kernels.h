@@ -242,6 +242,25 @@ struct DocScoreArgs {
   int64_t ldo;
 };
 hipError_t launch_doc_scores(const DocScoreArgs& a, int blocks, hipStream_t st);
+// lda_heldout_loglik (k_doc_completion): the scored tokens of Dh held-out
+// documents against the int32 nw rows.  A wave takes a document's tokens in
+// batches of doc_completion_batch(C): 64 up to C = 8, 16 above (the batch's
+// fp64 partial sums are registers beside the lane's C values of u_d).
+constexpr int doc_completion_batch(int C) { return C <= 8 ? 64 : 16; }
+struct DocCompletionArgs {
+  const int32_t* nw;        // [V * Kp]
+  const double* inv;        // [Kp]: 1 / (nwsum[k] + V beta), 0 past K (launch_heldout_inv)
+  const double* theta;      // [Dh * K]
+  const int64_t* doc_off;   // [Dh + 1] into words
+  const int32_t* words;     // every id in [0, V)
+  double* out;              // [Dh]
+  int64_t Dh;
+  int32_t K, Kp;
+  double beta;
+};
+hipError_t launch_heldout_inv(const int32_t* nwsum, double vbeta, int32_t K, int32_t Kp, double* inv,
+                              hipStream_t st);
+hipError_t launch_doc_completion(const DocCompletionArgs& a, int blocks, hipStream_t st);
 // range workers per block of the sampler kernel used for (C, sampler): 4
 // waves, 16 for the large-K sparse kernel (C >= 32), 8 for the half-wave
 // dense kernel (4 waves x 2 halves)

@@ -3755,6 +3755,110 @@ __global__ __launch_bounds__(256) void k_doc_scores(const DocScoreArgs a) {
   }
 }
 
+// lda_heldout_loglik: inv[k] = 1 / (nwsum[k] + V beta) in fp64, 0 for the
+// padded topics.
+__global__ __launch_bounds__(256) void k_heldout_inv(const int32_t* __restrict__ nwsum, double vbeta, int32_t K,
+                                                     int32_t Kp, double* __restrict__ inv) {
+  const int k = (int)(blockIdx.x * 256 + threadIdx.x);
+  if (k < Kp) inv[k] = k < K ? 1.0 / ((double)nwsum[k] + vbeta) : 0.0;
+}
+
+// a lane's C contiguous int32 of a row, in 16-byte loads from C = 4 on
+template <int C>
+__device__ __forceinline__ void load_row_slice(const int32_t* __restrict__ p, int32_t (&v)[C]) {
+  if constexpr (C == 1) {
+    v[0] = p[0];
+  } else if constexpr (C == 2) {
+    const int2 x = *reinterpret_cast<const int2*>(p);
+    v[0] = x.x;
+    v[1] = x.y;
+  } else {
+#pragma unroll
+    for (int i = 0; i < C / 4; ++i) {
+      const int4 x = reinterpret_cast<const int4*>(p)[i];
+      v[4 * i] = x.x;
+      v[4 * i + 1] = x.y;
+      v[4 * i + 2] = x.z;
+      v[4 * i + 3] = x.w;
+    }
+  }
+}
+
+// lda_heldout_loglik: document completion.  For held-out document d with
+// u_d[k] = theta_d[k] inv[k] and b_d = beta sum_k u_d[k],
+//   ll_d = sum_i log(sum_k u_d[k] nw[w_i, k] + b_d)
+// over its scored tokens.  One wave per document; lane l owns topics
+// [l C, (l + 1) C) (the samplers' ownership) and holds its C values of u_d in
+// registers.  The tokens go in batches of T: each token's row slice is dotted
+// with u_d into one of T per-lane partial sums (the T row loads are
+// independent, so several rows are in flight), a transposing butterfly
+// (T - 1 + log2(64 / T) exchanges instead of 6 T) leaves token t's sum in
+// every lane with lane % T == t, and lanes 0 .. T-1 take the batch's T logs
+// in parallel and keep a running sum each.  ll_d is the fixed-order wave sum
+// of those: no floating-point atomics, and the value depends on the
+// document's theta row and tokens alone.  A document without tokens gives 0.
+template <int C, int T>
+__global__ __launch_bounds__(256) void k_doc_completion(const DocCompletionArgs a) {
+  static_assert(T == 16 || T == 64, "the butterfly below takes T = 16 or 64");
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int32_t* __restrict__ nw = a.nw;
+  const int32_t* __restrict__ words = a.words;
+  const int k0 = lane * C;
+  for (int64_t d = (int64_t)blockIdx.x * 4 + wid; d < a.Dh; d += (int64_t)gridDim.x * 4) {
+    const int64_t t0 = a.doc_off[d], t1 = a.doc_off[d + 1];
+    double u[C], b = 0.0;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      u[c] = k0 + c < a.K ? a.theta[d * a.K + k0 + c] * a.inv[k0 + c] : 0.0;
+      b += u[c];
+    }
+    b = a.beta * wave_sum_d(b);
+    double ll = 0.0;
+    for (int64_t base = t0; base < t1; base += T) {
+      const int n = (int)(t1 - base < T ? t1 - base : T);   // wave-uniform
+      const int wv = lane < n ? words[base + lane] : 0;
+      double acc[T];
+      auto token = [&](int t) {
+        const int32_t* row = nw + (size_t)readlane_i(wv, t) * a.Kp + k0;
+        int32_t v[C];
+        load_row_slice<C>(row, v);
+        double s = 0.0;
+#pragma unroll
+        for (int c = 0; c < C; ++c) s += u[c] * (double)v[c];
+        acc[t] = s;
+      };
+      if (n == T) {
+#pragma unroll
+        for (int t = 0; t < T; ++t) token(t);
+      } else {
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+          acc[t] = 0.0;
+          if (t < n) token(t);
+        }
+      }
+      // transpose and sum: after the step with offset h a lane keeps the h
+      // tokens whose index agrees with its lane number in bit h (and above)
+#pragma unroll
+      for (int h = T / 2; h >= 1; h >>= 1) {
+        const bool up = (lane & h) != 0;
+#pragma unroll
+        for (int j = 0; j < h; ++j) {
+          const double keep = up ? acc[j + h] : acc[j], send = up ? acc[j] : acc[j + h];
+          acc[j] = keep + __shfl_xor(send, h);
+        }
+      }
+      double p = acc[0];
+#pragma unroll
+      for (int h = T; h < 64; h <<= 1) p += __shfl_xor(p, h);
+      const double lg = log(p + b);
+      if (lane < n) ll += lg;   // n <= T: lanes 0 .. n-1 hold tokens base + lane
+    }
+    ll = wave_sum_d(ll);
+    if (lane == 0) a.out[d] = ll;
+  }
+}
+
 // Word part: sum over nonzero nw cells of logGammaStirling(beta + count).
 __global__ __launch_bounds__(256) void k_ll_words(const int32_t* __restrict__ nw, int64_t V,
                                                   int32_t K, int32_t Kp, double beta,
@@ -4489,6 +4593,32 @@ hipError_t launch_doc_scores(const DocScoreArgs& a, int blocks, hipStream_t st) 
   else
     hipLaunchKernelGGL(k_doc_scores<DOC_SCORE_TILE>, dim3(blocks), dim3(256), lds, st, a);
   return hipGetLastError();
+}
+
+hipError_t launch_heldout_inv(const int32_t* nwsum, double vbeta, int32_t K, int32_t Kp, double* inv,
+                              hipStream_t st) {
+  hipLaunchKernelGGL(k_heldout_inv, dim3((Kp + 255) / 256), dim3(256), 0, st, nwsum, vbeta, K, Kp, inv);
+  return hipGetLastError();
+}
+
+template <int C>
+static hipError_t launch_doc_completion_t(const DocCompletionArgs& a, int blocks, hipStream_t st) {
+  hipLaunchKernelGGL((k_doc_completion<C, doc_completion_batch(C)>), dim3(blocks), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_doc_completion(const DocCompletionArgs& a, int blocks, hipStream_t st) {
+  if (a.Dh <= 0) return hipSuccess;
+  switch (a.Kp / 64) {
+    case 1: return launch_doc_completion_t<1>(a, blocks, st);
+    case 2: return launch_doc_completion_t<2>(a, blocks, st);
+    case 4: return launch_doc_completion_t<4>(a, blocks, st);
+    case 8: return launch_doc_completion_t<8>(a, blocks, st);
+    case 16: return launch_doc_completion_t<16>(a, blocks, st);
+    case 32: return launch_doc_completion_t<32>(a, blocks, st);
+    case 64: return launch_doc_completion_t<64>(a, blocks, st);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 hipError_t launch_ll_words(const int32_t* nw, int64_t V, int32_t K, int32_t Kp, double beta,

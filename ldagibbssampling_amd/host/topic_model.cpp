@@ -11,7 +11,9 @@
 //    statistics on sweeps with iteration > burninPeriod and
 //    iteration % saveSampleInterval == 0; optimizeAlpha + optimizeBeta when
 //    iteration > burninPeriod and iteration % optimizeInterval == 0;
-//    "<iteration> LL/token: x" every 10 iterations.
+//    "<iteration> LL/token: x" every 10 iterations.  Not Mallet's: with
+//    setHeldOut, "<iteration> held-out LL/token: x" every interval-th
+//    iteration (document completion on the device; training is unchanged).
 //  * optimizeAlpha: Dirichlet.learnParameters(alpha, topicDocCounts,
 //    docLengthCounts, 1.001, 1.0, 1), or learnSymmetricConcentration over the
 //    pooled histogram when usingSymmetricAlpha; histograms then cleared.
@@ -848,6 +850,7 @@ void ParallelTopicModel::optimizeBeta(const std::vector<int32_t>& hist, const st
 void ParallelTopicModel::estimate() {
   ensureShards();
   ll_trace_.clear();
+  held_trace_.clear();
   const double total_tokens = (double)numTokens();
   // Mallet's estimate() builds new WorkerRunnables whose alpha statistics
   // start empty (WorkerRunnable.initializeAlphaStatistics): statistics still
@@ -878,7 +881,8 @@ void ParallelTopicModel::estimate() {
   // between run as one batch
   auto work_after = [&](int32_t i) {
     const bool opt = i > burnin_period_ && optimize_interval_ != 0;
-    return i % 10 == 0 || (opt && (i % save_sample_interval_ == 0 || i % optimize_interval_ == 0));
+    return i % 10 == 0 || (opt && (i % save_sample_interval_ == 0 || i % optimize_interval_ == 0)) ||
+           (held_interval_ > 0 && i % held_interval_ == 0);
   };
   auto show_before = [&](int32_t i) { return show_topics_interval_ != 0 && i % show_topics_interval_ == 0; };
   for (int32_t it = 1; it <= num_iterations_; ++it) {
@@ -918,6 +922,19 @@ void ParallelTopicModel::estimate() {
       } else {
         log("<" + std::to_string(it) + ">");
       }
+    }
+    if (held_interval_ > 0 && it % held_interval_ == 0) {
+      // the held-out set against the counts as they stand after this sweep:
+      // reads nw / nwsum on shard 0 and writes only its own scratch
+      collect_ll();   // keeps the log in iteration order
+      const int64_t Dh = (int64_t)held_off_.size() - 1;
+      std::vector<double> doc_ll((size_t)Dh);
+      int64_t scored = 0;
+      const double ll = evaluate(Dh, held_off_.data(), held_words_.data(), held_iterations_, held_thinning_,
+                                 held_burn_in_, held_seed_, doc_ll.data(), &scored, nullptr);
+      const double per_token = scored > 0 ? ll / (double)scored : 0.0;
+      held_trace_.emplace_back(it, per_token);
+      log("<" + std::to_string(it) + "> held-out LL/token: " + java_number5(per_token));
     }
   }
   collect_ll();
@@ -1280,6 +1297,77 @@ void ParallelTopicModel::scoreTop(int32_t metric, int64_t Q, const double* theta
   }
 }
 
+double ParallelTopicModel::heldOutLogLik(int64_t Dh, const double* theta, const int64_t* doc_off,
+                                         const int32_t* words, double* doc_ll) {
+  ensureShards();
+  double total = 0.0;
+  check(lda_heldout_loglik(shards_->ctx[0], Dh, theta, doc_off, words, doc_ll, &total), "lda_heldout_loglik");
+  return total;
+}
+
+void ParallelTopicModel::completionSplit(int32_t V, int64_t Dh, const int64_t* doc_off, const int32_t* words,
+                                         std::vector<int64_t>& obs_off, std::vector<int32_t>& obs,
+                                         std::vector<int64_t>& sc_off, std::vector<int32_t>& sc) {
+  obs_off.assign((size_t)Dh + 1, 0);
+  sc_off.assign((size_t)Dh + 1, 0);
+  obs.clear();
+  sc.clear();
+  std::vector<int32_t> kept;
+  for (int64_t d = 0; d < Dh; ++d) {
+    kept.clear();
+    for (int64_t i = doc_off[d] - doc_off[0]; i < doc_off[d + 1] - doc_off[0]; ++i)
+      if (words[i] >= 0 && words[i] < V) kept.push_back(words[i]);
+    const size_t h = kept.size() / 2;
+    obs.insert(obs.end(), kept.begin(), kept.begin() + (std::ptrdiff_t)h);
+    sc.insert(sc.end(), kept.begin() + (std::ptrdiff_t)h, kept.end());
+    obs_off[(size_t)d + 1] = (int64_t)obs.size();
+    sc_off[(size_t)d + 1] = (int64_t)sc.size();
+  }
+}
+
+double ParallelTopicModel::evaluate(int64_t Dh, const int64_t* doc_off, const int32_t* words,
+                                    int32_t num_iterations, int32_t thinning, int32_t burn_in, uint64_t seed,
+                                    double* doc_ll, int64_t* tokens_scored, double* theta_out) {
+  ensureShards();
+  if (Dh < 0 || (Dh > 0 && (!doc_off || !doc_ll))) raise(LDA_ERR_INVALID_ARG, "bad documents");
+  for (int64_t d = 1; d <= Dh; ++d)
+    if (doc_off[d] < doc_off[d - 1]) raise(LDA_ERR_INVALID_ARG, "doc_off not monotone");
+  if (Dh > 0 && doc_off[Dh] > doc_off[0] && !words) raise(LDA_ERR_INVALID_ARG, "words is null");
+  std::vector<int64_t> obs_off, sc_off;
+  std::vector<int32_t> obs, sc;
+  completionSplit(V_, Dh, doc_off, words, obs_off, obs, sc_off, sc);
+  if (tokens_scored) *tokens_scored = (int64_t)sc.size();
+  double total = 0.0;
+  check(lda_doc_completion(shards_->ctx[0], Dh, obs_off.data(), obs.empty() ? nullptr : obs.data(), sc_off.data(),
+                           sc.empty() ? nullptr : sc.data(), num_iterations, thinning, burn_in, seed, doc_ll,
+                           &total, theta_out),
+        "lda_doc_completion");
+  return total;
+}
+
+void ParallelTopicModel::setHeldOut(int64_t Dh, const int64_t* doc_off, const int32_t* words, int32_t interval,
+                                    int32_t num_iterations, int32_t thinning, int32_t burn_in, uint64_t seed) {
+  if (interval < 0 || Dh < 0 || num_iterations < 0 || burn_in < 0 || thinning < 1)
+    raise(LDA_ERR_INVALID_ARG, "bad held-out settings");
+  if (interval > 0 && Dh > 0 && !doc_off) raise(LDA_ERR_INVALID_ARG, "null doc_off");
+  held_off_.assign(1, 0);
+  held_words_.clear();
+  held_interval_ = 0;
+  if (interval == 0) return;
+  for (int64_t d = 1; d <= Dh; ++d)
+    if (doc_off[d] < doc_off[d - 1]) raise(LDA_ERR_INVALID_ARG, "doc_off not monotone");
+  const int64_t n = Dh > 0 ? doc_off[Dh] - doc_off[0] : 0;
+  if (n > 0 && !words) raise(LDA_ERR_INVALID_ARG, "words is null");
+  held_off_.resize((size_t)Dh + 1);
+  for (int64_t d = 0; d <= Dh && Dh > 0; ++d) held_off_[(size_t)d] = doc_off[d] - doc_off[0];
+  held_words_.assign(words, words + n);
+  held_interval_ = interval;
+  held_iterations_ = num_iterations;
+  held_thinning_ = thinning;
+  held_burn_in_ = burn_in;
+  held_seed_ = seed;
+}
+
 }  // namespace lda_host
 
 // ------------------------------------------------------------------ C ABI
@@ -1490,6 +1578,23 @@ lda_status ldatm_get_ll_trace(ldatm* m, int32_t* iterations, double* ll, int32_t
   return LDA_OK;
 }
 
+lda_status ldatm_set_held_out(ldatm* m, int64_t Dh, const int64_t* doc_off, const int32_t* words, int32_t interval,
+                              int32_t num_iterations, int32_t thinning, int32_t burn_in, uint64_t seed) {
+  TM_CHECK(m);
+  return guard([&] { m->model.setHeldOut(Dh, doc_off, words, interval, num_iterations, thinning, burn_in, seed); });
+}
+
+lda_status ldatm_get_held_out_trace(ldatm* m, int32_t* iterations, double* ll, int32_t cap, int32_t* n) {
+  TM_CHECK(m);
+  const auto& t = m->model.heldOutTrace();
+  if (n) *n = (int32_t)t.size();
+  for (int32_t i = 0; i < cap && i < (int32_t)t.size(); ++i) {
+    if (iterations) iterations[i] = t[(size_t)i].first;
+    if (ll) ll[i] = t[(size_t)i].second;
+  }
+  return LDA_OK;
+}
+
 lda_status ldatm_model_log_likelihood(ldatm* m, double* out) {
   TM_CHECK(m);
   return guard([&] { *out = m->model.modelLogLikelihood(); });
@@ -1619,6 +1724,51 @@ lda_status ldatm_score(ldatm* m, int32_t metric, int64_t Dh, const int64_t* doc_
     }
     m->model.infer(Dh, doc_off, words, num_iterations, thinning, burn_in, seed, theta);
     m->model.scoreTheta(metric, Dh, theta, M, docs, scores);
+  });
+}
+
+lda_status ldatm_heldout_loglik(ldatm* m, int64_t Dh, const double* theta, const int64_t* doc_off,
+                                const int32_t* words, double* doc_ll, double* total) {
+  TM_CHECK(m);
+  if (Dh > 0 && !doc_ll) {
+    g_tm_error = "null doc_ll";
+    return LDA_ERR_INVALID_ARG;
+  }
+  return guard([&] {
+    const double t = m->model.heldOutLogLik(Dh, theta, doc_off, words, doc_ll);
+    if (total) *total = t;
+  });
+}
+
+lda_status ldatm_evaluate(ldatm* m, int64_t Dh, const int64_t* doc_off, const int32_t* words,
+                          int32_t num_iterations, int32_t thinning, int32_t burn_in, uint64_t seed,
+                          double* doc_ll, double* total, int64_t* tokens_scored, double* theta_out) {
+  TM_CHECK(m);
+  if (Dh > 0 && !doc_ll) {
+    g_tm_error = "null doc_ll";
+    return LDA_ERR_INVALID_ARG;
+  }
+  return guard([&] {
+    const double t = m->model.evaluate(Dh, doc_off, words, num_iterations, thinning, burn_in, seed, doc_ll,
+                                       tokens_scored, theta_out);
+    if (total) *total = t;
+  });
+}
+
+lda_status ldatm_completion_split(int32_t num_types, int64_t Dh, const int64_t* doc_off, const int32_t* words,
+                                  int64_t* obs_off, int32_t* obs_words, int64_t* sc_off, int32_t* sc_words) {
+  if (Dh < 0 || !doc_off || !obs_off || !sc_off || (Dh > 0 && doc_off[Dh] > doc_off[0] && !words)) {
+    g_tm_error = "null argument";
+    return LDA_ERR_INVALID_ARG;
+  }
+  return guard([&] {
+    std::vector<int64_t> oo, so;
+    std::vector<int32_t> o, s;
+    lda_host::ParallelTopicModel::completionSplit(num_types, Dh, doc_off, words, oo, o, so, s);
+    std::copy(oo.begin(), oo.end(), obs_off);
+    std::copy(so.begin(), so.end(), sc_off);
+    if (obs_words) std::copy(o.begin(), o.end(), obs_words);
+    if (sc_words) std::copy(s.begin(), s.end(), sc_words);
   });
 }
 

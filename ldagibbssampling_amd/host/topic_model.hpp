@@ -122,6 +122,29 @@ class ParallelTopicModel {
   // numDocs() are -1 / NaN
   void scoreTop(int32_t metric, int64_t Q, const double* theta, int32_t n, int64_t* doc_ids, double* scores);
 
+  // ---- held-out evaluation by document completion (lda_heldout_loglik /
+  //      lda_doc_completion on shard 0: every shard holds the same global
+  //      counts, and the inference draws are keyed by a token's index in the
+  //      batch, so spreading the documents over shards would change theta) ----
+  // theta[Dh*K] and the scored tokens given; returns the total
+  double heldOutLogLik(int64_t Dh, const double* theta, const int64_t* doc_off, const int32_t* words,
+                       double* doc_ll);
+  // whole held-out documents: tokens outside [0, V) are dropped, then each
+  // document is split as completionSplit does; returns the total
+  double evaluate(int64_t Dh, const int64_t* doc_off, const int32_t* words, int32_t num_iterations,
+                  int32_t thinning, int32_t burn_in, uint64_t seed, double* doc_ll, int64_t* tokens_scored,
+                  double* theta_out);
+  // the first floor(L/2) kept tokens of each document are observed, the rest
+  // scored (corpus.document_completion_split after the out-of-vocabulary drop)
+  static void completionSplit(int32_t V, int64_t Dh, const int64_t* doc_off, const int32_t* words,
+                              std::vector<int64_t>& obs_off, std::vector<int32_t>& obs,
+                              std::vector<int64_t>& sc_off, std::vector<int32_t>& sc);
+  // a held-out set evaluated by estimate() after every interval-th sweep
+  // (interval 0: off); not part of the checkpoint
+  void setHeldOut(int64_t Dh, const int64_t* doc_off, const int32_t* words, int32_t interval,
+                  int32_t num_iterations, int32_t thinning, int32_t burn_in, uint64_t seed);
+  const std::vector<std::pair<int32_t, double>>& heldOutTrace() const { return held_trace_; }
+
  private:
   void ensureShards();
   void markDirty();
@@ -163,6 +186,12 @@ class ParallelTopicModel {
   uint32_t sweep_ = 0;  // Philox sweep counter carried across re-sharding
   std::vector<int32_t> doc_len_counts_, topic_doc_counts_;  // alpha statistics
   std::vector<std::pair<int32_t, double>> ll_trace_;
+  // setHeldOut: the documents and the inference settings, and estimate()'s trace
+  std::vector<int64_t> held_off_{0};
+  std::vector<int32_t> held_words_;
+  int32_t held_interval_ = 0, held_iterations_ = 100, held_thinning_ = 10, held_burn_in_ = 10;
+  uint64_t held_seed_ = 0;
+  std::vector<std::pair<int32_t, double>> held_trace_;
 };
 
 }  // namespace lda_host

@@ -386,6 +386,40 @@ class GibbsSampler:
                                           scores.ctypes.data), "lda_score_docs")
         return scores
 
+    def heldout_loglik(self, theta, doc_off, words):
+        """lda_heldout_loglik: the log likelihood of the scored tokens of Dh
+        held-out documents (doc_off[Dh + 1], words) under their topic
+        distributions theta[Dh, K] and the model's current counts, computed on
+        the device.  Returns (doc_ll[Dh], total) with total == sum of doc_ll
+        added in order."""
+        theta = capi.as_theta(theta, self.K)
+        off, w = capi.as_docs(doc_off, words, len(theta))
+        doc_ll = np.zeros(len(theta), dtype=np.float64)
+        total = C.c_double(0.0)
+        capi.check(self._L.lda_heldout_loglik(self._h, len(theta), theta.ctypes.data, off.ctypes.data,
+                                              w.ctypes.data if len(w) else None, doc_ll.ctypes.data,
+                                              C.addressof(total)), "lda_heldout_loglik")
+        return doc_ll, total.value
+
+    def doc_completion(self, obs_off, obs_words, sc_off, sc_words, n_iter: int = 100, thin: int = 10,
+                       burn_in: int = 10, seed: int = 0, return_theta: bool = False):
+        """lda_doc_completion: infer() on the observed halves, then
+        heldout_loglik() of the result on the scored halves, in one native
+        call.  Returns (doc_ll[Dh], total), and theta[Dh, K] (what infer()
+        gives for the same arguments) as a third value with return_theta."""
+        ooff, ow = capi.as_docs(obs_off, obs_words, what="obs_off")
+        Dh = len(ooff) - 1
+        soff, sw = capi.as_docs(sc_off, sc_words, Dh, what="sc_off")
+        doc_ll = np.zeros(Dh, dtype=np.float64)
+        theta = np.zeros((Dh, self.K), dtype=np.float64) if return_theta else None
+        total = C.c_double(0.0)
+        capi.check(self._L.lda_doc_completion(
+            self._h, Dh, ooff.ctypes.data, ow.ctypes.data if len(ow) else None, soff.ctypes.data,
+            sw.ctypes.data if len(sw) else None, int(n_iter), int(thin), int(burn_in),
+            int(seed) & (2**64 - 1), doc_ll.ctypes.data, C.addressof(total),
+            theta.ctypes.data if return_theta else None), "lda_doc_completion")
+        return (doc_ll, total.value, theta) if return_theta else (doc_ll, total.value)
+
     # ------------------------------------------- hyperparameter statistics
     def max_doc_length(self) -> int:
         m = C.c_int32()

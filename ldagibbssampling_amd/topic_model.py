@@ -84,6 +84,11 @@ TM_SIGNATURES = {
     "ldatm_score": (_i32, [_vp, _i32, C.c_int64, _vp, _vp, _i32, _i32, _i32, C.c_uint64, C.c_int64, _vp,
                            _vp, _vp]),
     "ldatm_score_top": (_i32, [_vp, _i32, C.c_int64, _vp, _i32, _vp, _vp]),
+    "ldatm_heldout_loglik": (_i32, [_vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "ldatm_evaluate": (_i32, [_vp, C.c_int64, _vp, _vp, _i32, _i32, _i32, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "ldatm_completion_split": (_i32, [_i32, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ldatm_set_held_out": (_i32, [_vp, C.c_int64, _vp, _vp, _i32, _i32, _i32, _i32, C.c_uint64]),
+    "ldatm_get_held_out_trace": (_i32, [_vp, _vp, _vp, _i32, C.POINTER(_i32)]),
     "ldatm_format_double": (_i32, [C.c_double, _i32, C.c_char_p, C.c_size_t]),
     "ldatm_last_error": (C.c_char_p, []),
 }
@@ -459,6 +464,104 @@ class ParallelTopicModel:
         _check(self._L.ldatm_score_top(self._h, m, len(theta), theta.ctypes.data, n, ids.ctypes.data,
                                        scores.ctypes.data), "topDocuments")
         return ids, scores
+
+
+    # ------------------------------------------------ held-out evaluation
+    def getHeldOutEvaluator(self) -> "HeldOutEvaluator":
+        return HeldOutEvaluator(self)
+
+    def heldOutLogLikelihood(self, theta, doc_off, words):
+        """ldatm_heldout_loglik: (doc_ll[Dh], total) of the scored tokens
+        (doc_off[Dh + 1], words, ids in [0, V)) under theta[Dh, K] and the
+        model's current counts, computed on the device."""
+        theta = capi.as_theta(theta, self.numTopics)
+        off, w = capi.as_docs(doc_off, words, len(theta))
+        doc_ll = np.zeros(len(theta), np.float64)
+        total = C.c_double(0.0)
+        _check(self._L.ldatm_heldout_loglik(self._h, len(theta), theta.ctypes.data, off.ctypes.data,
+                                            w.ctypes.data if len(w) else None, doc_ll.ctypes.data,
+                                            C.addressof(total)), "heldOutLogLikelihood")
+        return doc_ll, total.value
+
+    def setHeldOut(self, instances, interval: int, numIterations: int = 100, thinning: int = 10,
+                   burnIn: int = 10, seed: int = 0):
+        """estimate() evaluates `instances` as getHeldOutEvaluator().evaluate
+        does after every sweep it with it % interval == 0 (0 = off) and keeps
+        (it, held-out LL/token) in heldOutTrace().  Training is unchanged."""
+        interval = int(interval)
+        if interval < 0:
+            raise ValueError("interval must be >= 0")
+        off, w = _flatten(list(instances))
+        _check(self._L.ldatm_set_held_out(self._h, len(off) - 1, off.ctypes.data, w.ctypes.data if len(w) else None,
+                                          interval, int(numIterations), int(thinning), int(burnIn),
+                                          int(seed) & (2**64 - 1)), "setHeldOut")
+
+    def heldOutTrace(self):
+        """[(iteration, held-out LL/token)] of the last estimate()."""
+        n = C.c_int32()
+        _check(self._L.ldatm_get_held_out_trace(self._h, None, None, 0, C.byref(n)), "ldatm_get_held_out_trace")
+        it = np.zeros(n.value, np.int32)
+        ll = np.zeros(n.value, np.float64)
+        if n.value:
+            _check(self._L.ldatm_get_held_out_trace(self._h, it.ctypes.data, ll.ctypes.data, n.value,
+                                                    C.byref(n)), "ldatm_get_held_out_trace")
+        return list(zip(it.tolist(), ll.tolist()))
+
+
+class HeldOutResult:
+    """What HeldOutEvaluator.evaluate returns."""
+
+    def __init__(self, logLikelihood: float, tokens: int, perDocument, theta):
+        self.logLikelihood = float(logLikelihood)
+        self.tokens = int(tokens)
+        self.perDocument = perDocument
+        self.theta = theta
+
+    @property
+    def perplexity(self) -> float:
+        return float(np.exp(-self.logLikelihood / self.tokens)) if self.tokens else float("nan")
+
+    def __repr__(self):
+        return (f"HeldOutResult(logLikelihood={self.logLikelihood!r}, tokens={self.tokens}, "
+                f"perplexity={self.perplexity!r})")
+
+
+def completion_split(instances, num_types: int):
+    """The split HeldOutEvaluator.evaluate makes (ldatm_completion_split,
+    host-only): ids outside [0, num_types) are dropped, then the first
+    floor(L/2) tokens of each document are observed and the rest scored.
+    Returns (obs_off, obs_words, sc_off, sc_words)."""
+    off, w = _flatten(list(instances))
+    Dh = len(off) - 1
+    obs_off, sc_off = np.zeros(Dh + 1, np.int64), np.zeros(Dh + 1, np.int64)
+    obs, sc = np.zeros(len(w), np.int32), np.zeros(len(w), np.int32)
+    _check(load_tm().ldatm_completion_split(int(num_types), Dh, off.ctypes.data, w.ctypes.data if len(w) else None,
+                                            obs_off.ctypes.data, obs.ctypes.data, sc_off.ctypes.data,
+                                            sc.ctypes.data), "ldatm_completion_split")
+    return obs_off, obs[:obs_off[-1]].copy(), sc_off, sc[:sc_off[-1]].copy()
+
+
+class HeldOutEvaluator:
+    """Held-out log likelihood and perplexity by document completion against
+    the model's current counts, on the device (ldatm_evaluate)."""
+
+    def __init__(self, model: ParallelTopicModel):
+        self.model = model
+
+    def evaluate(self, instances, numIterations: int = 100, thinning: int = 10, burnIn: int = 10,
+                 seed: int = 0) -> HeldOutResult:
+        """Each document's first floor(L/2) in-vocabulary tokens are observed
+        (getSampledDistribution with these arguments), the rest are scored."""
+        off, w = _flatten(list(instances))
+        Dh = len(off) - 1
+        doc_ll = np.zeros(Dh, np.float64)
+        theta = np.zeros((Dh, self.model.numTopics), np.float64)
+        total, tokens = C.c_double(0.0), C.c_int64(0)
+        _check(self.model._L.ldatm_evaluate(self.model._h, Dh, off.ctypes.data, w.ctypes.data if len(w) else None,
+                                            int(numIterations), int(thinning), int(burnIn),
+                                            int(seed) & (2**64 - 1), doc_ll.ctypes.data, C.addressof(total),
+                                            C.addressof(tokens), theta.ctypes.data), "evaluate")
+        return HeldOutResult(total.value, tokens.value, doc_ll, theta)
 
 
 def _doc_ids(docs, model):
