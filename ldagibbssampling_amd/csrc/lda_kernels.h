@@ -128,10 +128,10 @@ int sample_blocks_per_cu(int C, bool frozen, int K, int half = 0);
 int half_topics_per_lane(int K);
 int quarter_topics_per_lane(int K);
 // rb: the large-K sampler's ring (C >= 32): 0 the default depth, nonzero
-// the short one for short rows (SB_RB_SHORT in lda_kernels.hip)
+// the short one for short rows (SB_RB_SHORT_ROUNDS below)
 hipError_t launch_sample_sparse(int C, bool frozen, const SampleParams& p, int blocks,
                                 hipStream_t st, int rb = 0);
-constexpr int SB_RB_SHORT_ROUNDS = 6;   // the short ring's rounds (SB_RB_SHORT's default)
+constexpr int SB_RB_SHORT_ROUNDS = 6;   // the short ring's register rounds
 int sample_sparse_blocks_per_cu(int C, bool frozen);
 // row totals of nw (saturating at Kp) -> host prefix -> capacity offsets
 hipError_t launch_row_caps(const int32_t* nw, int64_t V, int32_t Kp, int32_t* caps, hipStream_t st);
@@ -180,10 +180,6 @@ hipError_t launch_philox_draws(const int64_t* gtok, int64_t n, uint32_t c2, uint
                                uint32_t* out, hipStream_t st);
 hipError_t launch_init_z(int32_t* z, int64_t n, int32_t K, int64_t token_base, uint32_t k0,
                          uint32_t k1, hipStream_t st);
-#ifdef SB_X_DELTA_KERNEL
-hipError_t launch_delta_from_z(const int32_t* words, const int32_t* zold, const int32_t* z, int64_t n,
-                               int32_t Kp, int32_t* delta, hipStream_t st);
-#endif
 hipError_t launch_count(const int32_t* words, const int32_t* z, int64_t n, int32_t Kp,
                         int32_t* delta, int32_t* dsum, hipStream_t st);
 hipError_t launch_apply(int32_t* nw, int32_t* delta, int64_t n, hipStream_t st);

@@ -75,58 +75,24 @@ __device__ __forceinline__ float dpp_mov(float v) {
       float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, BOUND));
 }
 
-// Inclusive wavefront scan: row_shr:1,2,4,8 inside 16-lane rows (sources
-// outside the row read 0), row_bcast:15 into rows 1 and 3, row_bcast:31 into
-// rows 2 and 3.  Restated lane by lane in oracle/lda_oracle.c:wave_scan_emulate.
-#ifndef LDA_ASM_SCAN
-#define LDA_ASM_SCAN 1
-#endif
-#ifndef LDA_GPRIDX
-#define LDA_GPRIDX 1
-#endif
-#ifndef LDA_UPD_MASK
-#define LDA_UPD_MASK 1
-#endif
-#ifndef LDA_SALU_TRIM
-#define LDA_SALU_TRIM 1
-#endif
-// Keep the row prefetch a real pipeline: vmcnt counts vector memory
-// operations in issue order, and the compiler waits for row t while row t+1
-// stays in flight (vmcnt(P-1)) only when every token issues the same number
-// of them.  So the delta atomics are issued per 64-token chunk instead of per
-// token (LDA_CHUNK_DELTA), the prefetch load is unconditional, and the rare
-// int32-row load drains itself (LDA_WIDE_DRAIN).  Without them every token
-// waited vmcnt(0), i.e. for the row prefetched one token earlier.
-#ifndef LDA_WIDE_DRAIN
-#define LDA_WIDE_DRAIN 1
-#endif
-#ifndef LDA_CHUNK_DELTA
-#define LDA_CHUNK_DELTA 1
-#endif
-#ifndef LDA_SALU_COUNT
-#define LDA_SALU_COUNT 1
-#endif
-#ifndef LDA_WORD_FLAG
-#define LDA_WORD_FLAG 1
-#endif
+// The row prefetch of the dense samplers is a real pipeline: vmcnt counts
+// vector memory operations in issue order, and the compiler waits for row t
+// while row t+1 stays in flight (vmcnt(P-1)) only when every token issues the
+// same number of them.  So the delta atomics are issued per 64-token chunk,
+// not per token, the prefetch load is unconditional, and the rare int32-row
+// load drains itself.  Otherwise every token waits vmcnt(0), i.e. for the row
+// prefetched one token earlier.
 // s_waitcnt vmcnt(0) / vmcnt(1) (gfx9 encoding: expcnt and lgkmcnt left at their maxima)
 constexpr int kVmcnt0 = 0x0F70;
 constexpr int kVmcnt1 = 0x0F71;
 constexpr int kLgkmcnt0 = 0xC07F;   // lgkmcnt(0), vmcnt and expcnt left at their maxima
-// (a != b) ? m : 0 as s_cmp + s_cselect_b64
-__device__ __forceinline__ uint64_t select_mask_ne(int a, int b, uint64_t m) {
-  uint64_t r;
-  // the operands are wave-uniform; readfirstlane keeps them in SGPRs even
-  // where the compiler's divergence analysis cannot tell
-  a = __builtin_amdgcn_readfirstlane(a);
-  b = __builtin_amdgcn_readfirstlane(b);
-  asm("s_cmp_lg_u32 %1, %2\n\ts_cselect_b64 %0, %3, 0" : "=s"(r) : "s"(a), "s"(b), "s"(m) : "scc");
-  return r;
-}
-// (jo == J) ? m : 0 for J = 0..C-1 (immediate J: no constant in an SGPR)
+// (jo == J) ? m : 0 for J = 0..C-1 as s_cmp + s_cselect_b64 (immediate J: no
+// constant in an SGPR)
 template <int J>
 __device__ __forceinline__ uint64_t select_mask_c(int jo, uint64_t m) {
   uint64_t r;
+  // jo is wave-uniform; readfirstlane keeps it in an SGPR even where the
+  // compiler's divergence analysis cannot tell
   jo = __builtin_amdgcn_readfirstlane(jo);
   asm("s_cmp_eq_u32 %1, %2\n\ts_cselect_b64 %0, %3, 0" : "=s"(r) : "s"(jo), "n"(J), "s"(m) : "scc");
   return r;
@@ -145,14 +111,6 @@ __device__ __forceinline__ int first_lane_or(uint64_t m, int none) {
   asm("s_ff1_i32_b64 %0, %1\n\ts_min_u32 %0, %0, %2" : "=&s"(r) : "s"(m), "s"(none) : "scc");
   return r;
 }
-// (jo == j) ? m : 0 as s_cmp + s_cselect_b64 (the compiler splits the 64-bit
-// select in two and adds an s_and)
-__device__ __forceinline__ uint64_t select_mask(int jo, int j, uint64_t m) {
-  uint64_t r;
-  jo = __builtin_amdgcn_readfirstlane(jo);
-  asm("s_cmp_eq_u32 %1, %2\n\ts_cselect_b64 %0, %3, 0" : "=s"(r) : "s"(jo), "s"(j), "s"(m) : "scc");
-  return r;
-}
 // c + bit l of m (s_bitcmp1_b64 sets SCC, s_addc_u32 adds it)
 __device__ __forceinline__ int add_lane_bit(int c, uint64_t m, int l) {
   l = __builtin_amdgcn_readfirstlane(l);
@@ -160,22 +118,20 @@ __device__ __forceinline__ int add_lane_bit(int c, uint64_t m, int l) {
   asm("s_bitcmp1_b64 %1, %2\n\ts_addc_u32 %0, %0, 0" : "+s"(c) : "s"(m), "s"(l) : "scc");
   return c;
 }
+// Inclusive wavefront scan: row_shr:1,2,4,8 inside 16-lane rows (sources
+// outside the row read 0), row_bcast:15 into rows 1 and 3, row_bcast:31 into
+// rows 2 and 3.  Restated lane by lane in oracle/lda_oracle.c:wave_scan_emulate.
 __device__ __forceinline__ float wave_incl_scan(float x) {
   x = dpp_mov<0x111, 0xf, true>(x) + x;
   x = dpp_mov<0x112, 0xf, true>(x) + x;
   x = dpp_mov<0x114, 0xf, true>(x) + x;
   x = dpp_mov<0x118, 0xf, true>(x) + x;
-#if LDA_ASM_SCAN
   // The two broadcast steps as one masked DPP add each: rows outside the row
-  // mask are not written and keep x (= x + 0 of the two-instruction form).
+  // mask are not written and keep x (an add of 0 there).
   // s_nop 1: a VALU-written VGPR needs two wait states before a DPP read.
   asm("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
       "s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf"
       : "+v"(x));
-#else
-  x = x + dpp_mov<0x142, 0xa, false>(x);
-  x = x + dpp_mov<0x143, 0xc, false>(x);
-#endif
   return x;
 }
 
@@ -200,18 +156,15 @@ __device__ __forceinline__ void wave_lds_fence() { __builtin_amdgcn_fence(__ATOM
 // The next work range of a consumer (a wave, or a 16-lane row of the
 // quarter-wave kernel): its first is static -- consumer `id` of `count`
 // takes range id -- and later ones come from the queue, offset by count.
-// A launch's first grab was a burst of same-address atomics from every
-// consumer at once; a small corpus (C1: ~1000 ranges, one per wave) now
+// A first grab from the queue would be a burst of same-address atomics from
+// every consumer at once; a small corpus (C1: ~1000 ranges, one per wave)
 // takes none.  Which consumer samples which range never changes a result
 // (draws are keyed by the global token index).  The wave kernels pass the
 // result through uniform_i: the id derives from threadIdx.x, which the
 // compiler cannot tell is wave-uniform, and every branch on the range's
-// bounds downstream of it had become an exec-mask branch (scalar work).
-#ifndef LDA_STATIC_FIRST
-#define LDA_STATIC_FIRST 1
-#endif
+// bounds downstream of it would become an exec-mask branch (scalar work).
 __device__ __forceinline__ int first_or_queued(bool first, int id, int count, int queued) {
-  return (LDA_STATIC_FIRST && first) ? id : (LDA_STATIC_FIRST ? count : 0) + queued;
+  return first ? id : count + queued;
 }
 
 template <int C>
@@ -298,26 +251,9 @@ typedef float pkf32 __attribute__((ext_vector_type(2)));
 
 // Minimum waves per SIMD the compiler must fit the dense sampler into (a few
 // spilled registers are cheaper than a lost wave: A/B on C4 at C = 8, 7 waves
-// with 5 spills vs 6 without is +6%).  SAMPLE_WPE_C<C> overrides for A/B runs.
+// with 5 spills vs 6 without is +6%).
 template <int C>
-constexpr int sample_waves_per_eu() {
-#if defined(SAMPLE_WPE_C1)
-  if (C == 1) return SAMPLE_WPE_C1;
-#endif
-#if defined(SAMPLE_WPE_C2)
-  if (C == 2) return SAMPLE_WPE_C2;
-#endif
-#if defined(SAMPLE_WPE_C4)
-  if (C == 4) return SAMPLE_WPE_C4;
-#endif
-#if defined(SAMPLE_WPE_C8)
-  if (C == 8) return SAMPLE_WPE_C8;
-#endif
-#if defined(SAMPLE_WPE_C16)
-  if (C == 16) return SAMPLE_WPE_C16;
-#endif
-  return C == 8 ? 7 : 1;
-}
+constexpr int kSampleWavesPerEu = C == 8 ? 7 : 1;
 
 // Lane i gets a[i + S] for i + S < 64, else b[i + S - 64] (a wave-wide
 // shift across two chunk registers; two ds_bpermutes).
@@ -329,7 +265,7 @@ __device__ __forceinline__ int shift_in(int a, int b, int lane) {
 }
 
 template <int C, int P, bool FROZEN>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sample_waves_per_eu<C>())))
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kSampleWavesPerEu<C>)))
 void k_sample(SampleParams p) {
   if (p.state_dev) {                                  // a graph-launched sweep (lda_sweep)
     p.c2 = p.state_dev[0];
@@ -363,7 +299,6 @@ void k_sample(SampleParams p) {
 #pragma unroll
   for (int j = 0; j < C; ++j) inv_r[j] = p.inv[lane * C + j];
   const float beta = p.beta;
-  const uint64_t lt2_mask = __ballot(lane < 2);
   const int last_lane = (p.K - 1) / C;
   const uint64_t last_mask = __ballot(lane <= last_lane);
   const int last_j_tail = (p.K - 1) % C;
@@ -375,7 +310,7 @@ void k_sample(SampleParams p) {
   bool first_range = true;
   while (true) {
     int r = 0;
-    if ((!LDA_STATIC_FIRST || !first_range) && lane == 0) r = atomicAdd(p.queue, 1);
+    if (!first_range && lane == 0) r = atomicAdd(p.queue, 1);
     r = uniform_i(first_or_queued(first_range, (int)blockIdx.x * 4 + wid, (int)gridDim.x * 4, uniform_i(__shfl(r, 0))));
     first_range = false;
     if (r >= p.num_ranges) break;
@@ -391,7 +326,7 @@ void k_sample(SampleParams p) {
     // topic zo_ -> zn_): two wave-wide atomics per 64 tokens; the 32-bit cell
     // index is valid because lda_create keeps V*Kp < 2^32
     auto flush_delta = [&](int w_, int zo_, int zn_) {
-      if (!FROZEN && LDA_CHUNK_DELTA && p.delta && zn_ != zo_) {
+      if (!FROZEN && p.delta && zn_ != zo_) {
         const uint32_t row = (uint32_t)w_ * (uint32_t)KP;
         atomicAdd(p.delta + (row + (uint32_t)zo_), -1);
         atomicAdd(p.delta + (row + (uint32_t)zn_), 1);
@@ -400,8 +335,7 @@ void k_sample(SampleParams p) {
       }
     };
 
-    // --- chunk registers: chunk c (cw, cz, cu, cn, cf), c+1 (w1, z1, f1), c+2 (w2, z2);
-    // f = 1 when the word's row holds a count > 65535 (read the int32 row)
+    // --- chunk registers: chunk c (cw, cz, cu, cn), c+1 (w1, z1), c+2 (w2, z2)
     int cbase = 0;
     int cw = 0, cz = 0, w1 = 0, z1 = 0, w2 = 0, z2 = 0;
     if (lane < nt) {
@@ -416,18 +350,12 @@ void k_sample(SampleParams p) {
       w2 = wrd[128 + lane];
       z2 = zr[128 + lane];
     }
-    // kWordFlag: the int32-row flag rides in bit 31 of the word registers
-    // (one readlane per token for both; word ids are < 2^31)
-    constexpr bool kWordFlag = LDA_WORD_FLAG;
+    // bit 31 of a word register is set when the word's row holds a count
+    // > 65535 (read the int32 row): one readlane per token for both; word
+    // ids are < 2^31
     constexpr int kWordMask = 0x7FFFFFFF;
-    int cf = 0, f1 = 0;
-    if constexpr (kWordFlag) {
-      cw |= (int)wide_of[cw] << 31;
-      w1 |= (int)wide_of[w1] << 31;
-    } else {
-      cf = (int)wide_of[cw];
-      f1 = (int)wide_of[w1];
-    }
+    cw |= (int)wide_of[cw] << 31;
+    w1 |= (int)wide_of[w1] << 31;
     int cn = cz;
     float cu = u01(draw_u32(gbase + (uint64_t)lane, p.c2, p.c3, p.k0, p.k1));
     // word (and, for the inv_m1 prefetch, topic) of token cbase + lane + P:
@@ -474,11 +402,9 @@ void k_sample(SampleParams p) {
             cbase += 64;
             cw = w1;
             cz = z1;
-            cf = f1;
             w1 = w2;
             z1 = z2;
-            if constexpr (kWordFlag) w1 |= (int)wide_of[w1] << 31;
-            else f1 = (int)wide_of[w1];
+            w1 |= (int)wide_of[w1] << 31;
             cn = cz;
             cu = u01(draw_u32(gbase + (uint64_t)(cbase + lane), p.c2, p.c3, p.k0, p.k1));
             if (cbase + 128 + lane < nt) {
@@ -510,12 +436,8 @@ void k_sample(SampleParams p) {
         const int w = wf & kWordMask;
         const int zo = readlane_i(cz, idx);
         const float u = readlane_f(cu, idx);
-        const bool wide = kWordFlag ? wf < 0 : readlane_i(cf, idx) != 0;
-#if LDA_SALU_TRIM
+        const bool wide = wf < 0;
         const int lo = (int)((uint32_t)zo / C), jo = (int)((uint32_t)zo % C);
-#else
-        const int lo = zo / C, jo = zo % C;
-#endif
 
         // lane 0: add the previous token back under its new topic kp (deferred
         // from its draw; inc = 0 at a document's first token), then remove
@@ -544,11 +466,11 @@ void k_sample(SampleParams p) {
         // with s_set_gpr_idx (one move each for reading c_old and patching b)
         // instead of a select per element and a lane mask per element (C4:
         // 5.93 -> 6.26 G tok/s, although the tuples spill 9 more VGPRs).
-        constexpr bool kGprIdx = LDA_GPRIDX && C >= 8;
+        constexpr bool kGprIdx = C >= 8;
         // C = 8 rows as 9-wide vectors: hipcc expands a dynamic index into
         // selects for up to 8 elements, and indexes 9 or more with
         // s_set_gpr_idx (the 9th register is never addressed: jo < C)
-        constexpr int CV = (kGprIdx && C == 8) ? 9 : C;
+        constexpr int CV = C == 8 ? 9 : C;
         typedef int32_t civ __attribute__((ext_vector_type(CV)));
         typedef float cfv __attribute__((ext_vector_type(CV)));
         civ cfull;
@@ -556,12 +478,10 @@ void k_sample(SampleParams p) {
           const int32_t* wr = nw + (int64_t)w * KP + lane * C;
 #pragma unroll
           for (int j = 0; j < C; ++j) cfull[j] = wr[j];
-#if LDA_WIDE_DRAIN
           // hipcc lays the 16-bit branch out as a fall-through successor of
           // this block: without this wait, this load in flight into cfull
           // makes it wait vmcnt(0) there too
           __builtin_amdgcn_s_waitcnt(kVmcnt0);
-#endif
         } else {
 #pragma unroll
           for (int j = 0; j < C; ++j) cfull[j] = row16_count<C>(rows[s], j);
@@ -569,7 +489,6 @@ void k_sample(SampleParams p) {
         // the own-token-corrected factor of z_old, from lane lo's own row
         // element (exact: a 16-bit row holds every count below 65536)
         int32_t c_old;
-#if LDA_SALU_TRIM
         // one 64-bit lane mask per element: lane lo where j == jo, else none
         // (two SALU ops each; selecting under it is exact on lane lo, the
         // only lane whose value is used)
@@ -583,11 +502,6 @@ void k_sample(SampleParams p) {
 #pragma unroll
           for (int j = 1; j < C; ++j) c_old = __builtin_amdgcn_inverse_ballot_w64(jmask[j]) ? cfull[j] : c_old;
         }
-#else
-        c_old = cfull[0];
-#pragma unroll
-        for (int j = 1; j < C; ++j) c_old = (j == jo) ? cfull[j] : c_old;
-#endif
         const float bc = FROZEN ? 0.0f : ((float)(c_old - 1) + beta) * cinv;
         cfv bw;
         if constexpr (C >= 2) {
@@ -611,11 +525,7 @@ void k_sample(SampleParams p) {
         float acc = 0.0f;
 #pragma unroll
         for (int j = 0; j < C; ++j) {
-#if LDA_SALU_TRIM
           const float b = (kGprIdx || FROZEN) ? bw[j] : (__builtin_amdgcn_inverse_ballot_w64(jmask[j]) ? bc : bw[j]);
-#else
-          const float b = (!FROZEN && j == jo && own_old) ? bc : bw[j];
-#endif
           acc = __builtin_fmaf(a[j], b, acc);
           S[j] = acc;
         }
@@ -629,7 +539,6 @@ void k_sample(SampleParams p) {
         // T of lane lstar - 1 (0 for lane 0): the scan shifted one lane up
         const float E = readlane_f(dpp_mov<0x138, 0xf, true>(T), lstar);
         // every lane counts its own prefix against lane lstar's E; lstar's count is the one used
-#if LDA_SALU_COUNT
         // one compare per element straight into a lane mask, and lane l*'s
         // bit added on the scalar unit (s_bitcmp1 + s_addc): 12 VALU for the
         // count at C = 8 instead of 21
@@ -644,21 +553,6 @@ void k_sample(SampleParams p) {
         } else {
           cnt = add_lane_bit(cnt, __ballot(E + S[0] <= thr), lstar);
         }
-#else
-        int cl = 0;
-        if constexpr (C >= 2) {
-          // E + S_j in packed pairs (each half an IEEE add)
-#pragma unroll
-          for (int j = 0; j < C; j += 2) {
-            const pkf32 es = (pkf32){E, E} + (pkf32){S[j], S[j + 1]};
-            cl += (es.x <= thr) ? 1 : 0;
-            cl += (es.y <= thr) ? 1 : 0;
-          }
-        } else {
-          cl = (E + S[0] <= thr) ? 1 : 0;
-        }
-        const int cnt = readlane_i(cl, lstar);
-#endif
         // cnt in [0, last valid topic of lstar] or C (padded topics add 0)
         const int lim = lstar < last_lane ? C - 1 : last_j_tail;
         const int jsel = cnt < lim ? cnt : lim;
@@ -669,25 +563,6 @@ void k_sample(SampleParams p) {
         inc = 1;
         // lane idx <- kn under a scalar lane mask (no per-lane compare)
         cn = __builtin_amdgcn_inverse_ballot_w64(1ull << (uint32_t)idx) ? kn : cn;
-        if constexpr (!FROZEN && !LDA_CHUNK_DELTA) {
-#if LDA_UPD_MASK
-          // lanes 0 and 1 when the topic changed: one s_cmp + s_cselect; the
-          // 32-bit cell index is valid because lda_create keeps V*Kp < 2^32
-          if (__builtin_amdgcn_inverse_ballot_w64(select_mask_ne(kn, zo, lt2_mask))) {
-            const int k = lane == 0 ? zo : kn;
-            const int v = lane == 0 ? -1 : 1;
-            atomicAdd(p.delta + ((uint32_t)w * (uint32_t)KP + (uint32_t)k), v);
-            atomicAdd(&bsum[k], v);
-          }
-#else
-          if (kn != zo && lane < 2) {
-            const int k = lane == 0 ? zo : kn;
-            const int v = lane == 0 ? -1 : 1;
-            atomicAdd(&p.delta[(int64_t)w * KP + k], v);
-            atomicAdd(&bsum[k], v);
-          }
-#endif
-        }
 
     };
     // keep the pipeline full: the row of token t+P into slot s
@@ -1120,6 +995,13 @@ done:
 //   S_j = fma(a_j, b_j, S_{j-1});  T = inclusive row scan (row_shr 1,2,4,8)
 //   thr = u * T_15;  l* = first row-lane <= last with T > thr (else last)
 //   j*  = #{j : T_{l*-1} + S_j <= thr} clamped to the last valid topic
+
+// Waves per SIMD of the training kernel: 5 (96 VGPRs + 24 B/lane of spill at
+// CH = 8) is +7% on C2 after burn-in, equal near init, over the unconstrained
+// 108 VGPRs / 4 waves; 6 waves spill 76 B and lose 25%
+// (profiles/r02/quarter/ab).  The frozen kernel fits 5 unforced.
+constexpr int kQuarterWavesPerEu = 5;
+
 template <int CH>
 __device__ __forceinline__ void load_row16_q(uint32_t (&r)[(CH + 1) / 2], const uint16_t* __restrict__ p) {
   if constexpr (CH == 8) {
@@ -1153,13 +1035,6 @@ __device__ __forceinline__ float row_scan16_q(float x) {
   x = dpp_mov<0x118, 0xf, true>(x) + x;
   return x;
 }
-__device__ __forceinline__ int row_scan16_i(int x) {
-  x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xf, 0xf, true);
-  x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xf, 0xf, true);
-  x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xf, 0xf, true);
-  x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xf, 0xf, true);
-  return x;
-}
 // lane (row base + i) of v, i per lane (ds_bpermute)
 __device__ __forceinline__ int row_get_i(int v, int rowbase, int i) {
   return __builtin_amdgcn_ds_bpermute((rowbase + i) << 2, v);
@@ -1168,23 +1043,9 @@ __device__ __forceinline__ float row_get_f(float v, int rowbase, int i) {
   return __builtin_bit_cast(float, row_get_i(__builtin_bit_cast(int, v), rowbase, i));
 }
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 template <int CH, int P, bool FROZEN>
-// 5 waves per SIMD for the training kernel (96 VGPRs + 24 B/lane of spill
-// at CH = 8): +7% on C2 after burn-in, equal near
-// init, over the unconstrained 108 VGPRs / 4 waves; 6 waves spill 76 B and
-// lose 25% (profiles/r02/quarter/ab).  The frozen kernel fits 5 unforced.
-#ifndef QUARTER_WPE
-#define QUARTER_WPE 5
-#endif
-// 1: the word factors and the prefix-count sums two topics per packed fp32
-// instruction (round 6 A/B)
-#ifndef QUARTER_PK
-#define QUARTER_PK 0
-#endif
-#define QUARTER_ATTR __attribute__((amdgpu_waves_per_eu(FROZEN ? 4 : QUARTER_WPE)))
-__global__ __launch_bounds__(256) QUARTER_ATTR void k_sample_quarter(SampleParams p) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FROZEN ? 4 : kQuarterWavesPerEu)))
+void k_sample_quarter(SampleParams p) {
   if (p.state_dev) {                                  // a graph-launched sweep (lda_sweep)
     p.c2 = p.state_dev[0];
     p.beta = __uint_as_float(p.state_dev[1]);
@@ -1266,7 +1127,7 @@ __global__ __launch_bounds__(256) QUARTER_ATTR void k_sample_quarter(SampleParam
             loaded = 0;
             while (true) {
               int r = 0;
-              if ((!LDA_STATIC_FIRST || !first_range) && ql == 0) r = atomicAdd(p.queue, 1);
+              if (!first_range && ql == 0) r = atomicAdd(p.queue, 1);
               r = first_or_queued(first_range, ((int)blockIdx.x * 4 + wid) * 4 + (lane >> 4),
                                   (int)gridDim.x * 16, row_get_i(r, rb, 0));
               first_range = false;
@@ -1421,29 +1282,6 @@ __global__ __launch_bounds__(256) QUARTER_ATTR void k_sample_quarter(SampleParam
       const float bc = FROZEN ? 0.0f : ((float)(c_old - 1) + beta) * cinv;
       float S[CH];
       float acc = 0.0f;
-#if QUARTER_PK
-      // the word factors two topics per instruction (v_pk_add_f32 /
-      // v_pk_mul_f32: the same IEEE operations, element for element)
-      float bw[CH];
-#pragma unroll
-      for (int j = 0; j < CH; j += 2) {
-        if (j + 1 < CH) {
-          const f32x2 cf = {(float)cfull[j], (float)cfull[j + 1]};
-          const f32x2 iv = {inv_r[j], inv_r[j + 1]};
-          const f32x2 bb = {beta, beta};
-          const f32x2 r = (cf + bb) * iv;
-          bw[j] = r.x;
-          bw[j + 1] = r.y;
-        } else {
-          bw[j] = ((float)cfull[j] + beta) * inv_r[j];
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < CH; ++j) {
-        acc = __builtin_fmaf(a[j], own[j] ? bc : bw[j], acc);
-        S[j] = acc;
-      }
-#else
 #pragma unroll
       for (int j = 0; j < CH; ++j) {
         const float bw = ((float)cfull[j] + beta) * inv_r[j];
@@ -1451,7 +1289,6 @@ __global__ __launch_bounds__(256) QUARTER_ATTR void k_sample_quarter(SampleParam
         acc = __builtin_fmaf(a[j], b, acc);
         S[j] = acc;
       }
-#endif
       const float T = row_scan16_q(acc);
       const float thr = u * row_bcast15_f(T);
       // l* = #{row-lanes with T <= thr} (T is monotone), clamped to the last:
@@ -1463,25 +1300,8 @@ __global__ __launch_bounds__(256) QUARTER_ATTR void k_sample_quarter(SampleParam
       // lane l*'s is the draw's (E = T_{l*-1}), fetched once
       const float E = dpp_mov<0x111, 0xf, true>(T);
       int cl = 0;
-#if QUARTER_PK
-      {
-        const f32x2 ee = {E, E};
-#pragma unroll
-        for (int j = 0; j < CH; j += 2) {
-          if (j + 1 < CH) {
-            const f32x2 sj = {S[j], S[j + 1]};
-            const f32x2 es = ee + sj;
-            cl += (es.x <= thr) ? 1 : 0;
-            cl += (es.y <= thr) ? 1 : 0;
-          } else {
-            cl += (E + S[j] <= thr) ? 1 : 0;
-          }
-        }
-      }
-#else
 #pragma unroll
       for (int j = 0; j < CH; ++j) cl += (E + S[j] <= thr) ? 1 : 0;
-#endif
       const int cnt = row_get_i(cl, rb, ls);
       const int lim = ls < last_lane ? CH - 1 : last_j_tail;
       const int kn = ls * CH + (cnt < lim ? cnt : lim);
@@ -1595,7 +1415,7 @@ __global__ __launch_bounds__(256) void k_sample_sparse(SampleParams p) {
   bool first_range = true;
   while (true) {
     int r = 0;
-    if ((!LDA_STATIC_FIRST || !first_range) && lane == 0) r = atomicAdd(p.queue, 1);
+    if (!first_range && lane == 0) r = atomicAdd(p.queue, 1);
     r = uniform_i(first_or_queued(first_range, (int)blockIdx.x * 4 + wid, (int)gridDim.x * 4, uniform_i(__shfl(r, 0))));
     first_range = false;
     if (r >= p.num_ranges) break;
@@ -1892,91 +1712,36 @@ __global__ __launch_bounds__(256) void k_sample_sparse(SampleParams p) {
 // Work distribution and LDS are v8's: 16-wave blocks, a block-wide float2
 // {inv, ainv} table and per-wave 16-bit document counts (documents < 65536
 // tokens).  The word part streams rounds of 64 entries: the first RB rounds
-// of the next tokens sit in a ring of NS slots (refilled right after a token
-// has used its own rounds, so every wait covers loads issued at least one
-// token earlier), as bounded buffer loads whose range ends at the row's last
+// of the next tokens sit in a ring of NS slots (a slot is refilled at the
+// start of the token after the one that used it, so every wait covers loads
+// issued at least one token earlier), as bounded buffer loads whose range ends at the row's last
 // entry: the zero padding of a row's last round (k_build_sparse) is never
 // fetched.  Count changes go out per 64-token chunk (lane i: token i).
-#ifndef SB_RB
-#define SB_RB 12
-#endif
-#ifndef SB_NS
-#define SB_NS 2
-#endif
-#ifndef SB_RB_SHORT
-#define SB_RB_SHORT 6
-#endif
-#ifndef SB_NS_SHORT
-#define SB_NS_SHORT 4
-#endif
-// rows past the register rounds: batches of SB_BATCH rounds, double-buffered;
-// each lane keeps its running sum after each of the first SB_NB batches so a
+//
+// Tuning constants (C5 A/Bs of rounds 5 and 6).
+// The ring: kSbNs slots of kSbRb register rounds by default, kSbNsShort slots
+// of SB_RB_SHORT_ROUNDS (lda_kernels.h) for corpora of short rows
+constexpr int kSbRb = 12;
+constexpr int kSbNs = 2;
+constexpr int kSbNsShort = 4;
+// rows past the register rounds: batches of kSbBatch rounds, double-buffered;
+// each lane keeps its running sum after each of the first kSbNb batches so a
 // draw in a long row re-reads one batch of the selected lane
-#ifndef SB_BATCH
-#define SB_BATCH 4
-#endif
-#ifndef SB_NB
-#define SB_NB 2
-#endif
-// 1: the ring refill of token t+NS-1 issued last in token t, after the
-// long-row batches and the draw's rare paths, whose loads are waited for
-// right after they are issued (in-order vmcnt: such a wait drains every older
-// load, the refill included when it was issued before them)
-#ifndef SB_REFILL_LAST
-#define SB_REFILL_LAST 0
-#endif
+constexpr int kSbBatch = 4;
+constexpr int kSbNb = 2;
 // register rounds evaluated without a branch (the rest: one uniform branch
 // each); they share a basic block with the doc part's fixed-point chain
-#ifndef SB_RU
-#define SB_RU 2
-#endif
-// 1 (default since round 6): the A part's searches read LDS (the alpha
-// part's block from tab, the document part's per-lane sums with rotated
-// reads) instead of global memory -- one global round trip instead of two and
-// eight.  Same integers either way: 32 large-K parity tests green on both
-// builds; C5 2.18 -> 2.29e9 near init, 2.70 -> 2.77e9 after 30 sweeps
-// (profiles/r06/c5ab/).  0 keeps round 5's global-memory searches.
-#ifndef SB_APICK_LDS
-#define SB_APICK_LDS 1
-#endif
-// > 0 (default 4 since late round 6): the LDS reads (tab + document count)
-// of the first SB_LDS_BATCH register rounds are all issued, with the doc
-// part's, before the first is used -- one LDS round trip for those rounds
-// instead of one per round (the compiler had serialised them: one pair of
-// reads, wait, fma, the next pair); the sums are the same fma for fma.
-// SB_LDS_BATCH2 > 0: the next SB_LDS_BATCH2 rounds the same way, when the
-// row has them.  C5 with SB_TOKEN_LGKM0 (below), one session, both orders
-// (profiles/r06/ldsbatch/): near init 2.250 -> 2.294e9, after 30 sweeps
-// 2.730 -> 2.828e9; batches of 6 or all 12 rounds gain less.
-#ifndef SB_LDS_BATCH
-#define SB_LDS_BATCH 4
-#endif
-#ifndef SB_LDS_BATCH2
-#define SB_LDS_BATCH2 0
-#endif
-#ifndef SB_LDS_BATCH_ADDR
-#define SB_LDS_BATCH_ADDR 0
-#endif
-// 1 (default since late round 6): an lgkmcnt(0) at the end of every token,
-// where every LDS read of the token has been used anyway: without it the
-// waitcnt pass carried a rare path's pending LDS write across the loop's
-// join into the next token, as an lgkmcnt(0) between the batch's first reads
-// and the rest
-#ifndef SB_TOKEN_LGKM0
-#define SB_TOKEN_LGKM0 1
-#endif
-// 1 (A/B builds): the long rows' batches past the register rounds issue each
-// batch's LDS reads together as well
-#ifndef SB_LDS_BATCH_LONG
-#define SB_LDS_BATCH_LONG 0
-#endif
+constexpr int kSbRu = 2;
+// the LDS reads (tab + document count) of the first kSbLdsBatch register
+// rounds are all issued, with the doc part's, before the first is used: one
+// LDS round trip for those rounds instead of one per round; the sums are the
+// same fma for fma.  C5 near init 2.250 -> 2.294e9, after 30 sweeps 2.730 ->
+// 2.828e9; batches of 6 or all 12 rounds gain less (profiles/r06/ldsbatch/)
+constexpr int kSbLdsBatch = 4;
+// waves per block (they share the block-wide {inv, ainv} table)
+constexpr int kSbWaves = 16;
 // gfx9 buffer resource word 3 (raw 32-bit loads, bounds checked)
 constexpr int kBufWord3 = 0x00020000;
-#ifndef SB_WAVES
-#define SB_WAVES 16
-#endif
-template <int C>
-constexpr int sb_waves() { return SB_WAVES; }
 
 // Philox words x0, x1, x2 of a token's block, lane-parallel per 64-token
 // chunk (the large-K draw: x0 the draw, x1 the own-entry accept test, x2 the
@@ -2134,37 +1899,15 @@ __device__ __forceinline__ int wave_incl_scan_i(int x) {
   return x;
 }
 
-// SB_ND8 (measurement builds, round 6): the per-wave document counts as
-// bytes (documents of at most 255 tokens of one topic), 4 KiB per wave at
-// K = 4096 instead of 8 KiB, so that two 10-wave blocks (20 waves per CU,
-// with SB_WAVES 10 and SB_WPE 5) fit the 160 KiB of LDS
-#ifndef SB_ND8
-#define SB_ND8 0
-#endif
-#ifndef SB_WPE
-#define SB_WPE 0
-#endif
-#if SB_ND8 && !SB_APICK_LDS
-#error "SB_ND8 needs SB_APICK_LDS (the global-memory doc search reads 16-bit pairs)"
-#endif
-constexpr int kNdShift = SB_ND8 ? 2 : 1;     // counts per 32-bit LDS word: 4 or 2
-constexpr int kNdBits = SB_ND8 ? 8 : 16;
+// the per-wave document counts: 16 bits each, two per 32-bit LDS word
 __device__ __forceinline__ int nd16_get(const uint32_t* nd2, int k) {
-#if SB_ND8
-  return (int)reinterpret_cast<const uint8_t*>(nd2)[k];
-#endif
   return (int)reinterpret_cast<const uint16_t*>(nd2)[k];
 }
 
-// A SampleParams field read from the kernel-argument segment where it is used
-// (the kernel's only argument sits at offset 0).  The large-K sampler runs
-// out of SGPRs (36 spilled into VGPR lanes with every pointer held live);
-// pointers of rare paths (chunk and document switches, the doc-part search,
-// saturated rows) are re-read from the segment instead of held.
-// SB_X_COUNT (measurement builds only): per-path draw counters in p.trace
-// ([0] tokens, [1] A alpha part, [2] A doc part, [3] own-entry hits, [4]
-// re-draws) when the launch has a trace buffer (lda_debug_sample_trace;
-// plain sweeps have none)
+// SB_X_COUNT (measurement builds only, tools/count_paths.py): per-path draw
+// counters in p.trace ([0] tokens, [1] A alpha part, [2] A doc part, [3]
+// own-entry hits, [4] re-draws) when the launch has a trace buffer
+// (lda_debug_sample_trace; plain sweeps have none)
 #ifdef SB_X_COUNT
 #define SB_COUNT(i)                                                                   \
   do {                                                                                \
@@ -2176,80 +1919,23 @@ __device__ __forceinline__ int nd16_get(const uint32_t* nd2, int k) {
   do {              \
   } while (0)
 #endif
-// SB_GLOBAL_AS: the pointers a KARG read yields are used as global (address
-// space 1) pointers (KGLOBAL), so the count atomics are global_atomic, not
-// FLAT.  A FLAT operation still in flight (the no-return delta atomics of a
-// chunk switch) makes the waitcnt pass order every later vector memory wait
-// as vmcnt(0); merged into the loop's join, that had drained the ring of
-// prefetched rows at every token's first round (now vmcnt(14..19)).  2 (the
-// default since late round 6): the field itself still read as a FLAT load,
-// waited for where it is used.  1 (A/B): the field read through the kernarg
-// segment's address space -- scalar loads, 7% slower on C5.  0: round 5's
-// FLAT atomics.  C5, four sessions: +0.2-0.5% near init, +0.4-0.7% after
-// burn-in (profiles/r06/ldsbatch/r6v, r6w).
-#ifndef SB_GLOBAL_AS
-#define SB_GLOBAL_AS 2
-#endif
-// 1: the chunk switch waits vmcnt(1) for its chunk registers (round 4: with
-// FLAT atomics in flight the waitcnt pass had turned every later wait into
-// vmcnt(0)); 0 (A/B) leaves the waits to the compiler
-// 1 (default since late round 6): the alpha part's 64 block-end prefixes
-// (fixed for the sweep) in a register pair per lane for the whole launch
-// instead of one global round trip per A-alpha draw (8.7% of the draws).  Two
-// VGPRs spill in the 4 x 6 ring; still C5 +1.1-1.3% near init, +0.9% after
-// burn-in, two sessions (profiles/r06/ldsbatch/r6y)
-#ifndef SB_PFX_REG
-#define SB_PFX_REG 1
-#endif
-// 1 (default since late round 6): the A search's document part sums only the
-// nonzero count words of each lane's block (a mask first), not all C topics:
-// the same integers; C5 +0.5-0.7% near init, flat after burn-in
-// (profiles/r06/ldsbatch/r6z)
-#ifndef SB_ADOC_SPARSE
-#define SB_ADOC_SPARSE 1
-#endif
-// 1 (default since late round 6): a long row's first batch past the register
-// rounds loaded at the token's start instead of after the rounds, so its
-// memory latency overlaps them; C5 +2.7% near init, +1.5% after burn-in, two
-// sessions (profiles/r06/ldsbatch/r6ac, r6ad).  2 (the second batch too)
-// spills 6 VGPRs and loses.
-#ifndef SB_EARLY_BATCH
-#define SB_EARLY_BATCH 1
-#endif
-// 1 (default since late round 6): the ring slot of token t-1 refilled at
-// token t's start rather than after t's register rounds -- possible once no
-// FLAT operation forces vmcnt(0) (SB_GLOBAL_AS): C5 after 30 sweeps +1.3%,
-// near init within noise, two sessions (profiles/r06/ldsbatch/r6af)
-#ifndef SB_REFILL_FIRST
-#define SB_REFILL_FIRST 1
-#endif
-// 1 (A/B): Philox x1 (the own-entry accept test) computed on the own-entry
-// path instead of held per lane for the chunk (one VGPR)
-#ifndef SB_X1_LAZY
-#define SB_X1_LAZY 0
-#endif
-// 1 (default at the end of round 6): a new document's counts built from the
-// chunk registers instead of a memory read of its topics; the same counts,
-// C5 +0.3% after burn-in, flat near init (profiles/r06/ldsbatch/r6am)
-#ifndef SB_DOC_REGS
-#define SB_DOC_REGS 1
-#endif
-#ifndef SB_CHUNK_WAIT
-#define SB_CHUNK_WAIT 1
-#endif
-#if SB_GLOBAL_AS
-#if SB_GLOBAL_AS == 1
-#define KARG(field)                                                                                   \
-  (*(const volatile __attribute__((address_space(4))) decltype(SampleParams::field)*)(                 \
-      (const __attribute__((address_space(4))) char*)(__builtin_amdgcn_kernarg_segment_ptr()) +        \
-      offsetof(SampleParams, field)))
-#else
-// 2: the field read as before (a FLAT load, waited for where it is used),
-// only the pointers' own accesses global
+// A SampleParams field read from the kernel-argument segment where it is used
+// (the kernel's only argument sits at offset 0).  The large-K sampler runs
+// out of SGPRs (36 spilled into VGPR lanes with every pointer held live);
+// pointers of rare paths (chunk and document switches, the doc-part search,
+// saturated rows) are re-read from the segment instead of held.  The field
+// is read as a FLAT load, waited for where it is used (read through the
+// kernarg segment's own address space -- scalar loads -- C5 is 7% slower).
+// KGLOBAL: the pointer such a read yields, used as a global (address space
+// 1) pointer, so the count atomics (KATOMIC_ADD) are global_atomic, not FLAT.
+// A FLAT operation still in flight (the no-return delta atomics of a chunk
+// switch) makes the waitcnt pass order every later vector memory wait as
+// vmcnt(0); merged into the loop's join, that drains the ring of prefetched
+// rows at every token's first round (vmcnt(14..19) without).  C5 +0.2-0.5%
+// near init, +0.4-0.7% after burn-in (profiles/r06/ldsbatch/r6v, r6w).
 #define KARG(field)                                                                                   \
   (*reinterpret_cast<const volatile decltype(SampleParams::field)*>(                                  \
       (const char*)(__builtin_amdgcn_kernarg_segment_ptr()) + offsetof(SampleParams, field)))
-#endif
 template <typename T>
 __device__ __forceinline__ __attribute__((address_space(1))) T* kglobal(T* p) {
   return (__attribute__((address_space(1))) T*)p;
@@ -2260,29 +1946,17 @@ __device__ __forceinline__ const __attribute__((address_space(1))) T* kglobal(co
 }
 #define KGLOBAL(field) kglobal(KARG(field))
 #define KATOMIC_ADD(ptr, v) __hip_atomic_fetch_add((ptr), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#else
-#define KARG(field)                                                                                   \
-  (*reinterpret_cast<const volatile decltype(SampleParams::field)*>(                                  \
-      (const char*)(__builtin_amdgcn_kernarg_segment_ptr()) + offsetof(SampleParams, field)))
-#define KGLOBAL(field) KARG(field)
-#define KATOMIC_ADD(ptr, v) atomicAdd((ptr), (v))
-#endif
 template <int C, int NS, int RB, bool FROZEN>
-#if SB_WPE
-#define SB_ATTR __attribute__((amdgpu_waves_per_eu(SB_WPE, SB_WPE)))
-#else
-#define SB_ATTR
-#endif
-__global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(SampleParams p) {
+__global__ __launch_bounds__(64 * kSbWaves) void k_sample_big(SampleParams p) {
   extern __shared__ __attribute__((aligned(16))) int32_t smem[];
   constexpr int KP = C * 64;
-  constexpr int WB = sb_waves<C>();
+  constexpr int WB = kSbWaves;
   static_assert(NS >= 2 && NS <= 8, "ring slots");
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
   float2* tab = reinterpret_cast<float2*>(smem);                              // [KP] {inv, ainv}
-  constexpr int NDW = KP >> kNdShift;                                          // LDS words of a wave's counts
-  uint32_t* nd2 = reinterpret_cast<uint32_t*>(smem + 2 * KP) + wid * NDW;      // [KP/2] (16-bit) or [KP/4]
+  constexpr int NDW = KP / 2;                                                  // LDS words of a wave's counts
+  uint32_t* nd2 = reinterpret_cast<uint32_t*>(smem + 2 * KP) + wid * NDW;      // [KP/2]: two 16-bit counts each
 
   for (int i = threadIdx.x; i < KP; i += 64 * WB) tab[i] = p.big.tab[i];
   for (int i = threadIdx.x; i < WB * NDW; i += 64 * WB) smem[2 * KP + i] = 0;
@@ -2298,11 +1972,11 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
   auto row_ptr = [&](uint32_t o) -> const uint32_t* { return ent + ((uint64_t)o << 6); };
   const int32_t* __restrict__ row_nnz = p.row_nnz;
   const float4* __restrict__ tab_m1 = p.big.tab_m1;
-#if SB_PFX_REG
-  // the alpha part's block-end prefixes (fixed for the sweep) held per lane:
-  // the A search's block choice without a global round trip
+  // the alpha part's block-end prefixes (fixed for the sweep) held per lane
+  // for the whole launch: the A search's block choice (8.7% of the draws)
+  // without a global round trip.  Two VGPRs spill in the 4 x 6 ring; still C5
+  // +1.1-1.3% near init, +0.9% after burn-in (profiles/r06/ldsbatch/r6y)
   const uint64_t pfx_r = p.big.pfx[C * lane + C - 1];
-#endif
 
   auto fixp = [&](float x) -> uint32_t { return big_fix(x, S); };
   // one B term into the lane's running sum (SAT: the row holds a saturated
@@ -2328,7 +2002,7 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
   bool first_range = true;
   while (true) {
     int r = 0;
-    if ((!LDA_STATIC_FIRST || !first_range) && lane == 0) r = atomicAdd(p.queue, 1);
+    if (!first_range && lane == 0) r = atomicAdd(p.queue, 1);
     r = uniform_i(first_or_queued(first_range, (int)blockIdx.x * WB + wid, (int)gridDim.x * WB, uniform_i(__shfl(r, 0))));
     first_range = false;
     if (r >= p.num_ranges) break;
@@ -2361,19 +2035,9 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
     philox_x01(gbase + (uint64_t)lane, p.c2, p.c3, p.k0, p.k1, cx0, cx1);
     __builtin_amdgcn_s_waitcnt(kVmcnt0);
 
-    // SB_X_NODELTA: attribution builds only (wrong counts): no delta atomics.
-    // Not informative as run in round 6: without the changes the counts stay
-    // at their random start, the rows stay long and the sweep ran 2x slower.
-    // SB_X_DELTA_KERNEL: the same sampler with the count changes made right
-    // by k_delta_from_z after it (lda_capi.cpp), an A/B of where the atomics
-    // cost less (measurement builds only)
-#if defined(SB_X_NODELTA) || defined(SB_X_DELTA_KERNEL)
-    constexpr bool kDelta = false;
-#else
-    constexpr bool kDelta = !FROZEN;
-#endif
+    // the last chunk's count changes (lane i: token cbase + i)
     auto flush_chunk = [&]() {
-      if (kDelta && cn != cz) {
+      if (!FROZEN && cn != cz) {
         const uint64_t rb = (uint64_t)(uint32_t)cw * (uint64_t)KP;
         KATOMIC_ADD(KGLOBAL(delta) + (rb + (uint32_t)cz), -1);
         KATOMIC_ADD(KGLOBAL(delta) + (rb + (uint32_t)cn), 1);
@@ -2385,18 +2049,14 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
     auto build_doc = [&](int ts, int te) {
       uint64_t rl = 0;
       auto add_topic = [&](int k) {
-#if SB_ND8
-        atomicAdd(&nd2[k >> 2], 1u << (8 * (k & 3)));
-#else
         atomicAdd(&nd2[k >> 1], (k & 1) ? 0x10000u : 1u);
-#endif
         rl += fixp(tab[k].x);
       };
-#if SB_DOC_REGS
       // the document's topics from the chunk registers (tokens cbase ..
       // cbase + 191, not yet sampled: their old topics, as z in memory
       // holds them), memory only past them -- no load on a document switch
-      // of a document that fits
+      // of a document that fits; C5 +0.3% after burn-in, flat near init
+      // (profiles/r06/ldsbatch/r6am)
       {
         const int i0 = cbase + lane;
         if (i0 >= ts && i0 < te) add_topic(cz);
@@ -2404,9 +2064,6 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
         if (i0 + 128 >= ts && i0 + 128 < te) add_topic(z2);
       }
       for (int i = (ts > cbase + 192 ? ts : cbase + 192) + lane; i < te; i += 64) add_topic(zr[i]);
-#else
-      for (int i = ts + lane; i < te; i += 64) add_topic(zr[i]);
-#endif
       R = uniform_u64(wave_sum_u64(rl));
       wave_lds_fence();
     };
@@ -2494,10 +2151,8 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
             // but the z store just issued): a chunk register the compiler
             // believes in flight makes it wait vmcnt(0) where a token reads
             // it, i.e. drain the row ring
-#if SB_CHUNK_WAIT
             __builtin_amdgcn_s_waitcnt(kVmcnt1);
-#endif
-            if (kDelta && on != oz) {
+            if (!FROZEN && on != oz) {
               const uint64_t rb = (uint64_t)(uint32_t)ow * (uint64_t)KP;
               KATOMIC_ADD(KGLOBAL(delta) + (rb + (uint32_t)oz), -1);
               KATOMIC_ADD(KGLOBAL(delta) + (rb + (uint32_t)on), 1);
@@ -2514,16 +2169,16 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
             pk = -1;
           }
 
-#if SB_REFILL_FIRST
           {
             // the slot of token t-1 refilled first thing (its registers were
             // used up by token t-1): with no FLAT operation in flight the
             // waits for this token's own slot count past these loads
-            // (vmcnt(N)), and the next rows get a fuller token of lead
+            // (vmcnt(N)), and the next rows get a fuller token of lead; C5
+            // after 30 sweeps +1.3%, near init within noise
+            // (profiles/r06/ldsbatch/r6af)
             const int sp = (s + NS - 1) % NS;
             prefetch(ring[sp], rm1[sp], t + NS - 1);
           }
-#endif
           const int w = readlane_i(cw, idx);
           const int zo = readlane_i(cz, idx);
           const float u = u01((uint32_t)readlane_i((int)cx0, idx));
@@ -2538,17 +2193,10 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
           // fixed-point own-topic terms
           if (lane == 0) {
             const int pa = pk >= 0 ? pk : 0;
-#if SB_ND8
-            __hip_atomic_fetch_add(&nd2[pa >> 2], pk < 0 ? 0u : (1u << (8 * (pa & 3))), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_WAVEFRONT);
-            __hip_atomic_fetch_add(&nd2[zo >> 2], 0xFFFFFFFFu << (8 * (zo & 3)), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_WAVEFRONT);
-#else
             __hip_atomic_fetch_add(&nd2[pa >> 1], pk < 0 ? 0u : ((pa & 1) ? 0x10000u : 1u), __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_WAVEFRONT);
             __hip_atomic_fetch_add(&nd2[zo >> 1], (zo & 1) ? 0xFFFF0000u : 0xFFFFFFFFu, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_WAVEFRONT);
-#endif
           }
           wave_lds_fence();
           // the own topic's count after both updates (a plain read behind the
@@ -2567,7 +2215,7 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
           float acc = 0.0f;
           // the doc part, A_fx = sum_k nd_k F'_k + sum_k G'_k (exact), from
           // the slot's topic data; written out in the same basic block as the
-          // first SB_RU rounds (evaluated without a branch: a round past the
+          // first kSbRu rounds (evaluated without a branch: a round past the
           // row is zero entries, + 0), so the scheduler interleaves the two
           // chains.  A row holding a saturated count takes the general path.
           int64_t dG = 0;
@@ -2603,13 +2251,8 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
               Afx = S0 + R;
             }
             // A in fp32: beta 2^-S (hi 2^32 + lo), hi < 2^16 exact
-#ifdef SB_X_NOA
-            A_f = uniform_f((float)(uint32_t)S0 * bsig);   // attribution experiment only
-            (void)Afx;
-#else
             A_f = uniform_f(__builtin_fmaf((float)(uint32_t)uniform_i((int)(uint32_t)(Afx >> 32)), bsig_hi,
                                            (float)(uint32_t)uniform_i((int)(uint32_t)Afx) * bsig));
-#endif
           };
           auto rounds = [&](bool sat, int q0) __attribute__((always_inline)) {
 #pragma unroll
@@ -2621,42 +2264,22 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
           };
           // (the memory barriers keep the doc reads in the branches: hoisted
           // above the branch, their wait and conversions went with them)
-#if SB_EARLY_BATCH
           // a long row's first batch past the register rounds issued now, so
-          // its latency overlaps the rounds (zeros when the row has none)
-          uint32_t ea0[SB_BATCH];
-#if SB_EARLY_BATCH >= 2
-          uint32_t eb0[SB_BATCH];
-#endif
+          // its latency overlaps the rounds (zeros when the row has none);
+          // C5 +2.7% near init, +1.5% after burn-in (profiles/r06/ldsbatch/
+          // r6ac, r6ad); the second batch too spills 6 VGPRs and loses
+          uint32_t ea0[kSbBatch];
           {
             const __amdgpu_buffer_rsrc_t rb0 = __builtin_amdgcn_make_buffer_rsrc(
                 (void*)erow, (short)0, nr_all > RB ? n * 4 : 0, kBufWord3);
             int lo4 = lane * 4;
             asm volatile("" : "+v"(lo4));
 #pragma unroll
-            for (int b = 0; b < SB_BATCH; ++b) ea0[b] = __builtin_amdgcn_raw_buffer_load_b32(rb0, lo4 + (RB + b) * 256, 0, 0);
-#if SB_EARLY_BATCH >= 2
-            // and the second (a row shorter than it reads zeros: the bound
-            // is the row's own length)
-#pragma unroll
-            for (int b = 0; b < SB_BATCH; ++b)
-              eb0[b] = __builtin_amdgcn_raw_buffer_load_b32(rb0, lo4 + (RB + SB_BATCH + b) * 256, 0, 0);
-#endif
+            for (int b = 0; b < kSbBatch; ++b) ea0[b] = __builtin_amdgcn_raw_buffer_load_b32(rb0, lo4 + (RB + b) * 256, 0, 0);
           }
-#endif
           if (!row_sat) {
             asm volatile("" ::: "memory");
-#if SB_LDS_BATCH > 0
-            constexpr int BQ = SB_LDS_BATCH < RB ? SB_LDS_BATCH : RB;
-#if SB_LDS_BATCH_ADDR
-            // the rounds' topics first, so that every read below issues back
-            // to back (no address arithmetic between them to reuse a register
-            // still awaited)
-            int tq[BQ];
-#pragma unroll
-            for (int q = 0; q < BQ; ++q) tq[q] = (int)(ring[s][q] & ENT_TOPIC_MASK);
-            __builtin_amdgcn_sched_barrier(0);
-#endif
+            constexpr int BQ = kSbLdsBatch < RB ? kSbLdsBatch : RB;
             const DocReads dr = doc_reads();
             // every batched round's reads (a round past the row reads topic
             // 0's entries: harmless, its count is 0 and it is skipped below)
@@ -2664,65 +2287,21 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
             int ndq[BQ];
 #pragma unroll
             for (int q = 0; q < BQ; ++q) {
-#if SB_LDS_BATCH_ADDR
-              const int t_ = tq[q];
-#else
               const int t_ = (int)(ring[s][q] & ENT_TOPIC_MASK);
-#endif
               tbq[q] = tab[t_];
               ndq[q] = nd16_get(nd2, t_);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int q = 0; q < BQ; ++q) {
-              if (q < SB_RU || q < nr_all) {
+              if (q < kSbRu || q < nr_all) {
                 const float coef = __builtin_fmaf((float)ndq[q], tbq[q].x, tbq[q].y);
                 acc = __builtin_fmaf((float)(ring[s][q] >> ENT_TOPIC_BITS), coef, acc);
               }
               accq[q] = acc;
             }
             doc_part(dr);
-#if SB_LDS_BATCH2 > 0
-            constexpr int BQ2 = (BQ + SB_LDS_BATCH2 < RB ? BQ + SB_LDS_BATCH2 : RB);
-            if (BQ2 > BQ && nr_all > BQ) {
-              float2 tb2[BQ2 > BQ ? BQ2 - BQ : 1];
-              int nd2q[BQ2 > BQ ? BQ2 - BQ : 1];
-#pragma unroll
-              for (int q = BQ; q < BQ2; ++q) {
-                const int t_ = (int)(ring[s][q] & ENT_TOPIC_MASK);
-                tb2[q - BQ] = tab[t_];
-                nd2q[q - BQ] = nd16_get(nd2, t_);
-              }
-              __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-              for (int q = BQ; q < BQ2; ++q) {
-                if (q < nr_all) {
-                  const float coef = __builtin_fmaf((float)nd2q[q - BQ], tb2[q - BQ].x, tb2[q - BQ].y);
-                  acc = __builtin_fmaf((float)(ring[s][q] >> ENT_TOPIC_BITS), coef, acc);
-                }
-                accq[q] = acc;
-              }
-            } else {
-#pragma unroll
-              for (int q = BQ; q < BQ2; ++q) accq[q] = acc;
-            }
-            rounds(false, BQ2);
-#else
             rounds(false, BQ);
-#endif
-#else
-            const DocReads dr = doc_reads();
-            // the doc reads issue first; nothing moves across (the scheduler
-            // had issued them after the rounds' reads had been waited for)
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int q = 0; q < SB_RU; ++q) {
-              acc = term_acc(ring[s][q], w, false, acc);
-              accq[q] = acc;
-            }
-            doc_part(dr);
-            rounds(false, SB_RU);
-#endif
           } else {
             asm volatile("" ::: "memory");
             doc_part(doc_reads());
@@ -2736,98 +2315,43 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
 #pragma unroll
           for (int q = 0; q < RB; ++q) asm volatile("" ::"v"(ring[s][q]));
 
-          float accb[SB_NB];
+          float accb[kSbNb];
 #pragma unroll
-          for (int i = 0; i < SB_NB; ++i) accb[i] = 0.0f;
+          for (int i = 0; i < kSbNb; ++i) accb[i] = 0.0f;
           // the rounds past RB (long rows), streamed in double-buffered batches
           auto batches = [&](bool sat) {
             const __amdgpu_buffer_rsrc_t rb =
                 __builtin_amdgcn_make_buffer_rsrc((void*)erow, (short)0, n * 4, kBufWord3);
-            uint32_t ea[SB_BATCH];
+            uint32_t ea[kSbBatch];
             int lo4 = lane * 4;
             asm volatile("" : "+v"(lo4));
-#if SB_EARLY_BATCH
 #pragma unroll
-            for (int b = 0; b < SB_BATCH; ++b) ea[b] = ea0[b];
-#else
-#pragma unroll
-            for (int b = 0; b < SB_BATCH; ++b)
-              ea[b] = __builtin_amdgcn_raw_buffer_load_b32(rb, lo4 + (RB + b) * 256, 0, 0);
-#endif
+            for (int b = 0; b < kSbBatch; ++b) ea[b] = ea0[b];
             int mb = 0;
-            for (int q0 = RB; q0 < nr_all; q0 += SB_BATCH, ++mb) {
+            for (int q0 = RB; q0 < nr_all; q0 += kSbBatch, ++mb) {
               // the next batch's loads only when it exists: a load left
               // unconsumed keeps its registers "in flight" into the next token
-              uint32_t en[SB_BATCH];
-#if SB_EARLY_BATCH >= 2
-              if (q0 == RB) {
+              uint32_t en[kSbBatch];
+              if (q0 + kSbBatch < nr_all) {
+                const int vo = lo4 + (q0 + kSbBatch) * 256;
 #pragma unroll
-                for (int b = 0; b < SB_BATCH; ++b) en[b] = eb0[b];
-              } else
-#endif
-              if (q0 + SB_BATCH < nr_all) {
-                const int vo = lo4 + (q0 + SB_BATCH) * 256;
-#pragma unroll
-                for (int b = 0; b < SB_BATCH; ++b) en[b] = __builtin_amdgcn_raw_buffer_load_b32(rb, vo + b * 256, 0, 0);
+                for (int b = 0; b < kSbBatch; ++b) en[b] = __builtin_amdgcn_raw_buffer_load_b32(rb, vo + b * 256, 0, 0);
               } else {
 #pragma unroll
-                for (int b = 0; b < SB_BATCH; ++b) en[b] = 0u;
+                for (int b = 0; b < kSbBatch; ++b) en[b] = 0u;
               }
-#if SB_LDS_BATCH_LONG
-              if (!sat) {
-                // the batch's LDS reads issued together (one round trip per
-                // batch instead of one per round), then its fma in order
-                float2 tbb[SB_BATCH];
-                int ndb[SB_BATCH];
 #pragma unroll
-                for (int b = 0; b < SB_BATCH; ++b) {
-                  const int t_ = (int)(ea[b] & ENT_TOPIC_MASK);
-                  tbb[b] = tab[t_];
-                  ndb[b] = nd16_get(nd2, t_);
-                }
-                __builtin_amdgcn_sched_barrier(0);
+              for (int b = 0; b < kSbBatch; ++b) acc = term_acc(ea[b], w, sat, acc);
 #pragma unroll
-                for (int b = 0; b < SB_BATCH; ++b) {
-                  const float coef = __builtin_fmaf((float)ndb[b], tbb[b].x, tbb[b].y);
-                  acc = __builtin_fmaf((float)(ea[b] >> ENT_TOPIC_BITS), coef, acc);
-                }
-              } else {
+              for (int i = 0; i < kSbNb; ++i) accb[i] = (mb == i) ? acc : accb[i];
 #pragma unroll
-                for (int b = 0; b < SB_BATCH; ++b) acc = term_acc(ea[b], w, sat, acc);
-              }
-#else
-#pragma unroll
-              for (int b = 0; b < SB_BATCH; ++b) acc = term_acc(ea[b], w, sat, acc);
-#endif
-#pragma unroll
-              for (int i = 0; i < SB_NB; ++i) accb[i] = (mb == i) ? acc : accb[i];
-#pragma unroll
-              for (int b = 0; b < SB_BATCH; ++b) ea[b] = en[b];
+              for (int b = 0; b < kSbBatch; ++b) ea[b] = en[b];
             }
           };
-          auto refill = [&]() {
-            // every use of this token's ring slot is above: refill the slot
-            // of token t-1 (the loads cannot move above this point)
-            asm volatile("" : "+v"(acc)::"memory");
-            const int sp = (s + NS - 1) % NS;
-            prefetch(ring[sp], rm1[sp], t + NS - 1);
-          };
-#if SB_REFILL_LAST
           if (nr_all > RB) {
             if (!row_sat) batches(false);
             else batches(true);
           }
-#else
-#if !SB_REFILL_FIRST
-          refill();
-#else
-          (void)refill;
-#endif
-          if (nr_all > RB) {
-            if (!row_sat) batches(false);
-            else batches(true);
-          }
-#endif
           const float TB = wave_incl_scan(acc);
           const float sumB = readlane_f(TB, 63);
 
@@ -2858,23 +2382,20 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
             return Walk{(uint32_t)readlane_i((int)ex, sel), lo, hi};
           };
           // A: tfx in fixed point; the alpha part (prefix of G'), then the
-          // document part (prefix of nd F'), topics ascending
+          // document part (prefix of nd F'), topics ascending.  Both searches
+          // read LDS (the alpha part's block from tab, the document part's
+          // per-lane sums with rotated reads), not global memory: C5 2.18 ->
+          // 2.29e9 near init, 2.70 -> 2.77e9 after 30 sweeps (profiles/r06/c5ab/)
           auto pick_a = [&](float thr) -> int {
             const float t2 = thr - sumB;
             const uint64_t tfx = d2u64((double)t2 * isig);
             if (tfx < As) {
               SB_COUNT(1);
-#if SB_APICK_LDS
-              // the block of C topics: the block-end prefixes of G' (one
-              // global read); within it the prefix from LDS: G' = fixp(ainv)
-              // (+ dG at zo) split in 16-bit halves, each scanned in 32-bit
-              // lanes (< 2^22), so no second global round trip
+              // the block of C topics: the block-end prefixes of G' (pfx_r);
+              // within it the prefix from LDS: G' = fixp(ainv) (+ dG at zo)
+              // split in 16-bit halves, each scanned in 32-bit lanes (< 2^22)
               const int kc = C * lane + C - 1;
-#if SB_PFX_REG
               const uint64_t pc = pfx_r;
-#else
-              const uint64_t pc = KGLOBAL(big.pfx)[kc];
-#endif
               const int64_t vc = (int64_t)pc + ((!FROZEN && kc >= zo) ? dG : 0);
               const uint64_t mc = __ballot((uint64_t)vc > tfx);
               const int L = mc ? (int)__builtin_ctzll(mc) : 63;
@@ -2891,36 +2412,24 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
               const uint64_t incl = El + ((uint64_t)shi << 16) + slo;
               const uint64_t mf = __ballot(lane < C && incl > tfx);
               const int k = mf ? C * L + (int)__builtin_ctzll(mf) : last_topic;
-#else
-              const int kc = C * lane + C - 1;
-              const int64_t vc = (int64_t)KGLOBAL(big.pfx)[kc] + ((!FROZEN && kc >= zo) ? dG : 0);
-              const uint64_t mc = __ballot((uint64_t)vc > tfx);
-              const int L = mc ? (int)__builtin_ctzll(mc) : 63;
-              const int kf = C * L + (lane < C ? lane : C - 1);
-              const int64_t vf = (int64_t)KGLOBAL(big.pfx)[kf] + ((!FROZEN && kf >= zo) ? dG : 0);
-              const uint64_t mf = __ballot(lane < C && (uint64_t)vf > tfx);
-              const int k = mf ? C * L + (int)__builtin_ctzll(mf) : last_topic;
-#endif
               return k < last_topic ? k : last_topic;
             }
             const uint64_t tr = tfx - As;
             SB_COUNT(2);
-#if SB_APICK_LDS
             // lane l's topics [C l, C l + C), counts and F (= fixp(inv), as
             // k_big_tables makes it) from LDS, each lane starting its walk
             // at its own lane index: at the 2C-word lane stride of the
-            // tables, lanes in step would hit one bank (round 5 had read F
-            // from global memory, one round trip per 8 topics: the document
-            // part of A was ~4% of the draws near init and most of their
-            // time); the own topic's F' = Fm1 added as a correction on its lane
+            // tables, lanes in step would hit one bank (the document part of
+            // A is ~4% of the draws near init); the own topic's F' = Fm1
+            // added as a correction on its lane
             uint64_t ps = 0;
             {
-#if SB_ADOC_SPARSE && !SB_ND8
               // only the lane's nonzero count words: a mask from C / 8
               // 16-byte reads (starting at a lane-rotated chunk), then one
               // count word and one 16-byte tab read per nonzero word (a
               // document holds at most a few hundred topics of 4096); the
-              // same integer sum, in another order
+              // same integer sum, in another order; C5 +0.5-0.7% near init,
+              // flat after burn-in (profiles/r06/ldsbatch/r6z)
               const uint4* ndv = reinterpret_cast<const uint4*>(nd2) + lane * (C / 8);
               uint32_t nzm = 0;
 #pragma unroll 2
@@ -2943,44 +2452,9 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
                 const float4 t2 = *reinterpret_cast<const float4*>(tl + 2 * i);
                 ps += (uint64_t)(wv & 0xFFFFu) * fixp(t2.x) + (uint64_t)(wv >> 16) * fixp(t2.z);
               }
-#else
-#if SB_ND8
-              const uint8_t* ndh = reinterpret_cast<const uint8_t*>(nd2) + C * lane;
-#else
-              const uint16_t* ndh = reinterpret_cast<const uint16_t*>(nd2) + C * lane;
-#endif
-              const float2* tl = tab + C * lane;
-#pragma unroll 8
-              for (int j = 0; j < C; ++j) {
-                const int o = (j + lane) & (C - 1);
-                ps += (uint64_t)ndh[o] * fixp(tl[o].x);
-              }
-#endif
               if (!FROZEN && lane == (int)((uint32_t)zo / (uint32_t)C))
                 ps += (uint64_t)((int64_t)ndz * ((int64_t)Fm1z - (int64_t)Fz));
             }
-#else
-            // lane l's topics [C l, C l + C): the counts as 16-byte LDS reads
-            // (single u16 reads at a 2C-byte lane stride all hit one bank),
-            // F as 16-byte global reads; the own topic's F' = Fm1 added as a
-            // correction on its lane
-            uint64_t ps = 0;
-            {
-              const uint4* ndv = reinterpret_cast<const uint4*>(nd2 + lane * (C / 2));
-              const uint4* fv = reinterpret_cast<const uint4*>(KARG(big.F) + C * lane);
-#pragma unroll 1
-              for (int j8 = 0; j8 < C / 8; ++j8) {
-                const uint4 nv = ndv[j8];
-                const uint4 f0 = fv[2 * j8], f1 = fv[2 * j8 + 1];
-                ps += (uint64_t)(nv.x & 0xFFFFu) * f0.x + (uint64_t)(nv.x >> 16) * f0.y;
-                ps += (uint64_t)(nv.y & 0xFFFFu) * f0.z + (uint64_t)(nv.y >> 16) * f0.w;
-                ps += (uint64_t)(nv.z & 0xFFFFu) * f1.x + (uint64_t)(nv.z >> 16) * f1.y;
-                ps += (uint64_t)(nv.w & 0xFFFFu) * f1.z + (uint64_t)(nv.w >> 16) * f1.w;
-              }
-              if (!FROZEN && lane == (int)((uint32_t)zo / (uint32_t)C))
-                ps += (uint64_t)((int64_t)ndz * ((int64_t)Fm1z - (int64_t)Fz));
-            }
-#endif
             const uint64_t incl = wave_incl_scan_u64(ps);
             const uint64_t ml = __ballot(incl > tr);
             if (!ml) return last_topic;
@@ -2989,11 +2463,7 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
                                           (uint32_t)readlane_i((int)(uint32_t)incl, L - 1))
                                        : 0ull;
             const int kf = C * L + (lane < C ? lane : C - 1);
-#if SB_APICK_LDS
             const uint32_t ff = (!FROZEN && kf == zo) ? Fm1z : fixp(tab[kf].x);
-#else
-            const uint32_t ff = (!FROZEN && kf == zo) ? Fm1z : KGLOBAL(big.F)[kf];
-#endif
             const uint64_t wf = lane < C ? (uint64_t)nd16_get(nd2, kf) * ff : 0ull;
             const uint64_t i2 = wave_incl_scan_u64(wf);
             const uint64_t mf = __ballot(lane < C && El + i2 > tr);
@@ -3027,31 +2497,31 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
             } else {
               // lane lstar's rounds past RB: the first kept batch whose end
               // sum exceeds, else the rest; one re-walk of it
-              const int nbl = (nr - RB + SB_BATCH - 1) / SB_BATCH;
+              const int nbl = (nr - RB + kSbBatch - 1) / kSbBatch;
               int cb = 0;
 #pragma unroll
-              for (int i = 0; i < SB_NB; ++i)
+              for (int i = 0; i < kSbNb; ++i)
                 if (i < nbl && cb == i && readlane_f(accb[i], lstar) <= thrE) cb = i + 1;
               int r0, r1;
               float a;
-              if (cb < nbl && cb < SB_NB) {
-                r0 = RB + SB_BATCH * cb;
-                r1 = min(nr, r0 + SB_BATCH);
+              if (cb < nbl && cb < kSbNb) {
+                r0 = RB + kSbBatch * cb;
+                r1 = min(nr, r0 + kSbBatch);
                 a = readlane_f(accq[RB - 1], lstar);
 #pragma unroll
-                for (int i = 0; i < SB_NB; ++i)
+                for (int i = 0; i < kSbNb; ++i)
                   if (cb == i + 1) a = readlane_f(accb[i], lstar);
               } else if (cb < nbl) {
-                r0 = RB + SB_BATCH * SB_NB;
+                r0 = RB + kSbBatch * kSbNb;
                 r1 = nr;
-                a = readlane_f(accb[SB_NB - 1], lstar);
+                a = readlane_f(accb[kSbNb - 1], lstar);
               } else {
                 // none exceeds: the lane's last batch (its last round is taken)
-                r0 = RB + SB_BATCH * (nbl - 1);
+                r0 = RB + kSbBatch * (nbl - 1);
                 r1 = nr;
                 a = readlane_f(accq[RB - 1], lstar);
 #pragma unroll
-                for (int i = 0; i < SB_NB; ++i)
+                for (int i = 0; i < kSbNb; ++i)
                   if (nbl - 1 == i + 1) a = readlane_f(accb[i], lstar);
               }
               wk = rewalk(lstar, r0, r1, a, thrE);
@@ -3061,11 +2531,7 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
           } else {
             kn = pick_a(thr);
           }
-#ifdef SB_X_NOOWN
-          if (false) {   // attribution experiment only (wrong draws)
-#else
           if (!FROZEN && lstar >= 0 && kn == zo) {
-#endif
             // the own entry: keep zo with probability O / w, else one re-draw
             // with the entry's width replaced by O
             SB_COUNT(3);
@@ -3078,28 +2544,16 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
             const float wo = wk.hi - wk.lo;
             const float4 m1 = rm1[s];
             const float O = (float)(c > 0 ? c - 1 : 0u) * __builtin_fmaf((float)ndz, m1.x, m1.y);
-#if SB_X1_LAZY
-            // x1 of the token's Philox block computed here, on the own-entry
-            // path only, instead of held per lane for the whole chunk
-            uint32_t gt = (uint32_t)t;
-            asm volatile("" : "+s"(gt));
-            uint32_t y0, y1, y2;
-            philox_x012(gbase + (uint64_t)gt, p.c2, p.c3, p.k0, p.k1, y0, y1, y2);
-            const float u1 = u01(y1);
-#else
             const float u1 = u01((uint32_t)readlane_i((int)cx1, idx));
-#endif
             if (!(u1 * wo < O)) {
               // the re-draw (rare): x2 of the token's Philox block, computed
               // here (the token index passes an opaque register, so the block
               // is not hoisted into every token)
               SB_COUNT(4);
-#if !SB_X1_LAZY
               uint32_t gt = (uint32_t)t;
               asm volatile("" : "+s"(gt));
               uint32_t y0, y1, y2;
               philox_x012(gbase + (uint64_t)gt, p.c2, p.c3, p.k0, p.k1, y0, y1, y2);
-#endif
               const float s_lo = (lstar > 0 ? readlane_f(TB, lstar - 1) : 0.0f) + wk.lo;
               const float Tp = ((sumB - wo) + O) + A_f;
               const float thr2 = uniform_f(u01(y2) * Tp);
@@ -3120,19 +2574,12 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
               }
             }
           }
-#if SB_REFILL_LAST
-          // the refill after every load of this token (rare paths' waits
-          // would otherwise drain it; the next token's waits still count it)
-          refill();
-#endif
           pk = kn;
           cn = (lane == idx) ? kn : cn;
-#if SB_TOKEN_LGKM0
           // every LDS read of this token has been used by now: say so, so the
           // waitcnt pass does not carry a rare path's pending LDS write into
           // the next token's first reads as an lgkmcnt(0)
           __builtin_amdgcn_s_waitcnt(kLgkmcnt0);
-#endif
         }
       }
     }
@@ -3141,7 +2588,6 @@ __global__ __launch_bounds__(64 * sb_waves<C>()) SB_ATTR void k_sample_big(Sampl
     clear_doc();
   }
 }
-
 
 // Row capacities min(Kp, word total) (one wave per row).
 __global__ __launch_bounds__(256) void k_row_caps(const int32_t* __restrict__ nw, int64_t V,
@@ -4275,7 +3721,7 @@ static int occupancy_sparse_t() {
 template <int C, int NS, int RB, bool FROZEN>
 static size_t sparse_big_lds() {
   // {alpha, inv} table + per-wave 16-bit nd pairs; > 64 KiB at C = 64
-  constexpr size_t lds = (2 * 64 * C + sb_waves<C>() * ((64 * C) >> kNdShift)) * sizeof(int32_t);
+  constexpr size_t lds = (2 * 64 * C + kSbWaves * (64 * C / 2)) * sizeof(int32_t);
   static bool attr = [] {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sample_big<C, NS, RB, FROZEN>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
@@ -4286,24 +3732,24 @@ static size_t sparse_big_lds() {
 template <int C, int NS, int RB, bool FROZEN>
 static hipError_t launch_sparse_big_rb(const SampleParams& p, int blocks, hipStream_t st) {
   const size_t lds = sparse_big_lds<C, NS, RB, FROZEN>();
-  hipLaunchKernelGGL((k_sample_big<C, NS, RB, FROZEN>), dim3(blocks), dim3(64 * sb_waves<C>()),
+  hipLaunchKernelGGL((k_sample_big<C, NS, RB, FROZEN>), dim3(blocks), dim3(64 * kSbWaves),
                      lds, st, p);
   return hipGetLastError();
 }
-// rb: 0 for the default ring (SB_NS slots of SB_RB register rounds), else
-// the short one (SB_NS_SHORT x SB_RB_SHORT) for short rows (the caller's
+// rb: 0 for the default ring (kSbNs slots of kSbRb register rounds), else
+// the short one (kSbNsShort x SB_RB_SHORT_ROUNDS) for short rows (the caller's
 // choice, by timing both).  The same sums in the same order either way.
 template <int C, bool FROZEN>
 static hipError_t launch_sparse_big_t(const SampleParams& p, int blocks, hipStream_t st, int rb) {
-  if (!FROZEN && rb != 0) return launch_sparse_big_rb<C, SB_NS_SHORT, SB_RB_SHORT, FROZEN>(p, blocks, st);
-  return launch_sparse_big_rb<C, SB_NS, SB_RB, FROZEN>(p, blocks, st);
+  if (!FROZEN && rb != 0) return launch_sparse_big_rb<C, kSbNsShort, SB_RB_SHORT_ROUNDS, FROZEN>(p, blocks, st);
+  return launch_sparse_big_rb<C, kSbNs, kSbRb, FROZEN>(p, blocks, st);
 }
 template <int C, bool FROZEN>
 static int occupancy_sparse_big_t() {
   int nb = 0;
-  const size_t lds = sparse_big_lds<C, SB_NS, SB_RB, FROZEN>();
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_sample_big<C, SB_NS, SB_RB, FROZEN>,
-                                                   64 * sb_waves<C>(), lds) != hipSuccess)
+  const size_t lds = sparse_big_lds<C, kSbNs, kSbRb, FROZEN>();
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_sample_big<C, kSbNs, kSbRb, FROZEN>,
+                                                   64 * kSbWaves, lds) != hipSuccess)
     return 1;
   return nb > 0 ? nb : 1;
 }
@@ -4339,8 +3785,8 @@ int sample_sparse_blocks_per_cu(int C, bool frozen) {
 }
 
 int sample_waves_per_block(int C, bool sparse, int half) {
-  if (sparse && C == 32) return sb_waves<32>();
-  if (sparse && C == 64) return sb_waves<64>();
+  if (sparse && C == 32) return kSbWaves;
+  if (sparse && C == 64) return kSbWaves;
   if (!sparse && half == 1 && C <= 2) return 8;    // two range workers per wave
   if (!sparse && half == 2 && C <= 2) return 16;   // four range workers per wave
   return 4;
@@ -4425,30 +3871,6 @@ hipError_t launch_count(const int32_t* words, const int32_t* z, int64_t n, int32
   return hipGetLastError();
 }
 
-#ifdef SB_X_DELTA_KERNEL
-// measurement builds only: a token's count change from its topic before
-// (zold) and after (z) the sampling pass, as the sampler's own atomics make it
-__global__ __launch_bounds__(256) void k_delta_from_z(const int32_t* __restrict__ words,
-                                                      const int32_t* __restrict__ zold,
-                                                      const int32_t* __restrict__ z, int64_t n, int32_t Kp,
-                                                      int32_t* __restrict__ delta) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const int zo = zold[i], zn = z[i];
-    if (zo != zn) {
-      const int64_t rb = (int64_t)words[i] * Kp;
-      atomicAdd(delta + rb + zo, -1);
-      atomicAdd(delta + rb + zn, 1);
-    }
-  }
-}
-hipError_t launch_delta_from_z(const int32_t* words, const int32_t* zold, const int32_t* z, int64_t n,
-                               int32_t Kp, int32_t* delta, hipStream_t st) {
-  if (n <= 0) return hipSuccess;
-  const int blocks = (int)std::min<int64_t>((n + 255) / 256, 16384);
-  hipLaunchKernelGGL(k_delta_from_z, dim3(blocks), dim3(256), 0, st, words, zold, z, n, Kp, delta);
-  return hipGetLastError();
-}
-#endif
 
 hipError_t launch_apply(int32_t* nw, int32_t* delta, int64_t n, hipStream_t st) {
   const int64_t n4 = n / 4;
