@@ -430,6 +430,74 @@ lda_status lda_doc_completion(lda_ctx* ctx, int64_t Dh, const int64_t* obs_off, 
                               int32_t thinning, int32_t burn_in, uint64_t seed, double* doc_ll,
                               double* total, double* theta_out);
 
+/* The readouts of a trained model, selected on the device.
+ *
+ * lda_top_words: ParallelTopicModel.printTopWords / displayTopWords' selection
+ * [src/cmu_ron/TrainAndPredict.java:170] without the V x K table leaving the
+ * device.  For each topic k < K (padded topics are never reported): the words
+ * with nw[w,k] > 0 ordered by count descending, equal counts by ascending word
+ * id (Mallet's IDSorter over an array in id order); the first n of them in
+ * word_ids[k*n + i] and counts[k*n + i], i = 0 .. n-1.  Slots past the topic's
+ * last nonzero word hold id -1 and count 0.  It reads the global counts this
+ * shard holds (the int32 nw rows, V x Kp, kept for every sampler kind).
+ * Integer compares only, no atomics: (count << 32) | (0xFFFFFFFF - w) is a
+ * unique key per topic, so a topic's best n are one set however V is cut into
+ * slabs, and a call repeats bit for bit.
+ * Errors: LDA_ERR_INVALID_ARG for a NULL ctx or output, or n outside
+ * [1, LDA_TOP_WORDS_MAX]; LDA_ERR_STATE with a pending delta (call lda_apply
+ * first).
+ * Device scratch is grow-only and kept by the context: the slab lists, at
+ * most 1024 (slab, 64-topic group) waves x 64 topics x n keys of 8 bytes
+ * (512 KiB x n: 32 MiB at n = 64; Kp x n x 8 bytes when V <= 256), and the
+ * 8 K n bytes of the result, which is all that is copied to the host.  Waits
+ * for the context's stream. */
+#define LDA_TOP_WORDS_MAX 64
+lda_status lda_top_words(lda_ctx* ctx, int32_t n, int32_t* word_ids /*[K*n]*/, int32_t* counts /*[K*n]*/);
+
+/* lda_doc_top_topics: the m heaviest topics of documents of THIS shard,
+ * printDocumentTopics' selection [src/cmu_ron/TrainAndPredict.java:232], from
+ * the shard's current z on the device.  docs == NULL: documents
+ * [doc_begin, doc_begin + M); else docs[M] shard-local ids in any order,
+ * duplicates allowed (doc_begin must be 0), as lda_score_docs takes them.
+ * For the j-th document the topics are ordered by the weight
+ *     (alpha_k + n_dk) / (n_d + alphaSum)
+ * descending, in fp64 with exactly that expression ((double) n_dk and
+ * (double) n_d; alphaSum = alpha[0] + ... + alpha[K-1] added in that order in
+ * fp64), equal weights by ascending topic id; topics[j*m + i] and the topic's
+ * count n_dk in counts[j*m + i], i = 0 .. m-1.  With m > K the slots past K
+ * hold topic -1 and count 0.  An empty document ranks by alpha alone.  The
+ * device's quotient is IEEE-754 fp64 division (the library is built without
+ * fast-math and with -ffp-contract=off), so the order is the one the same
+ * expression gives on the host.  A document's row depends on that document
+ * alone, not on M, docs or the chunks, and a call repeats bit for bit.
+ * Errors: LDA_ERR_INVALID_ARG for a NULL ctx, m outside
+ * [1, LDA_TOP_TOPICS_MAX], M < 0, a document id or range outside [0, D), a
+ * list given with doc_begin != 0, or a NULL output with M > 0; LDA_ERR_STATE
+ * with a pending delta.  M = 0 succeeds and touches nothing.
+ * Device scratch is grow-only and kept by the context.  The documents are cut
+ * into chunks of at most min(2^20, 2^23 / (2 m)) documents, so the scratch
+ * never exceeds 32 MiB of results + 8 MiB of document ids (docs given),
+ * whatever M is.  Waits for the context's stream. */
+#define LDA_TOP_TOPICS_MAX 64
+lda_status lda_doc_top_topics(lda_ctx* ctx, int32_t m, int64_t doc_begin, int64_t M, const int64_t* docs,
+                              int32_t* topics /*[M*m]*/, int32_t* counts /*[M*m]*/);
+
+/* lda_doc_counts: the dense topic counts of documents of THIS shard,
+ * nd[j*K + k] = tokens of the j-th listed document with topic k (int32), from
+ * the shard's current z on the device -- lda_get_counts' nd rows for a list of
+ * documents.  doc_begin, M and docs as lda_doc_top_topics takes them (any
+ * order, duplicates allowed).  Integer counts: a row depends on its document
+ * alone and repeats bit for bit.
+ * Errors: LDA_ERR_INVALID_ARG for a NULL ctx, M < 0, a document id or range
+ * outside [0, D), a list given with doc_begin != 0, or a NULL nd with M > 0;
+ * LDA_ERR_STATE with a pending delta.  M = 0 succeeds and touches nothing.
+ * Device scratch is grow-only and kept by the context (shared with
+ * lda_doc_top_topics).  The documents are cut into chunks of at most
+ * min(2^20, max(1, 2^23 / K)) documents, so the scratch never exceeds 32 MiB
+ * of rows + 8 MiB of document ids (docs given), whatever M is.  Waits for the
+ * context's stream. */
+lda_status lda_doc_counts(lda_ctx* ctx, int64_t doc_begin, int64_t M, const int64_t* docs, int32_t* nd /*[M*K]*/);
+
 /* Mallet-layout adapter: typeTopicCounts as packed (count << topic_bits) |
  * topic rows sorted descending, rows[row_off[w] .. row_off[w+1]) with
  * row_off[V+1]; row length = min(K, typeTotal[w]) exactly as Mallet allocates
@@ -535,8 +603,9 @@ void lda_debug_fail_host_alloc(int32_t nth);
  * accept / re-draw), sequential sweeps recount under LDA_COUNT_RECOUNT,
  * lda_exchange_unpack_lists, lda_counts_checksum; 7 -- lda_set_exchange_cells
  * (four 8-bit cells per packed word); 8 -- lda_score_docs.
- * lda_heldout_loglik and lda_doc_completion came later and only add symbols,
- * so the version stays 8. */
+ * lda_heldout_loglik and lda_doc_completion, then lda_top_words,
+ * lda_doc_top_topics and lda_doc_counts came later and only add symbols, so
+ * the version stays 8. */
 #define LDA_ABI_VERSION 8
 const char* lda_version(void);
 int32_t lda_abi_version(void);

@@ -145,6 +145,42 @@ lda_status ldatm_get_counts(ldatm* m, int32_t* nw /*[V*K] or NULL*/, int32_t* nw
 /* getTopicProbabilities(doc): (n_dk + alpha_k) / sum_k (n_dk + alpha_k). */
 lda_status ldatm_get_topic_probabilities(ldatm* m, int64_t doc, double* out /*[K]*/);
 
+/* The readouts of a trained model, selected on the device (lda_top_words,
+ * lda_doc_top_topics, lda_doc_counts of lda_mi355x.h): no V x K
+ * table and no copy of the topic assignments crosses to the host.
+ *
+ * ldatm_top_words: per topic k < K the n words with the largest count, count
+ * descending, equal counts by ascending word id (displayTopWords' order);
+ * word_ids[K*n] and counts[K*n], slots past a topic's last nonzero word -1 and
+ * 0.  Runs on shard 0: every shard holds the same global counts, so the result
+ * does not depend on the number of shards, bit for bit.
+ * Errors: LDA_ERR_INVALID_ARG for a NULL model or output, or n outside
+ * [1, LDA_TOP_WORDS_MAX] (checked before any device work).  Scratch as
+ * lda_top_words.  Waits for shard 0's stream. */
+lda_status ldatm_top_words(ldatm* m, int32_t n, int32_t* word_ids /*[K*n]*/, int32_t* counts /*[K*n]*/);
+/* ldatm_doc_top_topics: for the global document ids docs[M] (any order,
+ * duplicates allowed), or docs == NULL: all documents, M = the model's D, the
+ * mtop topics with the largest weight (alpha_k + n_dk) / (n_d + alphaSum),
+ * equal weights by ascending topic id; topics[M*mtop] and the topics' counts
+ * counts[M*mtop], slots past K -1 and 0.  alphaSum is the sum of the model's
+ * alpha added in topic order (lda_doc_top_topics), which is what
+ * ldatm_get_hyper reports after an optimisation; see documentTopics in DESIGN
+ * 9d for a model whose alpha_sum holds other bits.
+ * ldatm_doc_counts: the same documents' dense count rows nd[M*K].
+ * Both map the global ids onto the shards' document ranges as
+ * ldatm_score_theta does; each shard answers for its own documents on its own
+ * device and the rows are scattered back into the caller's order.  A
+ * document's row depends on that document alone: not on M, the list or the
+ * number of shards, bit for bit.
+ * Errors: LDA_ERR_INVALID_ARG for a NULL model, mtop outside
+ * [1, LDA_TOP_TOPICS_MAX], M < 0, a document id outside [0, D), M != D without
+ * a list, or a NULL output with M > 0.  M = 0 succeeds and touches nothing.
+ * Device scratch per shard as the lda_ calls bound it; the host holds one
+ * shard's rows while it scatters them.  Waits for the shards' streams. */
+lda_status ldatm_doc_top_topics(ldatm* m, int32_t mtop, int64_t M, const int64_t* docs,
+                                int32_t* topics /*[M*mtop]*/, int32_t* counts /*[M*mtop]*/);
+lda_status ldatm_doc_counts(ldatm* m, int64_t M, const int64_t* docs, int32_t* nd /*[M*K]*/);
+
 /* printDocumentTopics(File) (threshold 0, max -1 = all) and its text:
  * "#doc source topic proportion ...", then per document
  * "<doc> <source|null-source> <topic> <weight> ... \n" (weights descending,

@@ -31,6 +31,9 @@ MAX_EXCHANGE_PARTS = 4
 SAMPLERS = {"dense": 0, "sparse": 1}
 COUNT_UPDATE = {"auto": 0, "recount": 1, "delta": 2}
 SCORE_METRICS = {"cosine": 0, "mse": 1}
+# LDA_TOP_WORDS_MAX / LDA_TOP_TOPICS_MAX of lda_mi355x.h
+TOP_WORDS_MAX = 64
+TOP_TOPICS_MAX = 64
 
 
 def score_metric(metric) -> int:
@@ -136,6 +139,9 @@ SIGNATURES = {
     "lda_heldout_loglik": (C.c_int32, [_vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     "lda_doc_completion": (C.c_int32, [_vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_uint64, _vp, _vp, _vp]),
+    "lda_top_words": (C.c_int32, [_vp, C.c_int32, _vp, _vp]),
+    "lda_doc_top_topics": (C.c_int32, [_vp, C.c_int32, C.c_int64, C.c_int64, _vp, _vp, _vp]),
+    "lda_doc_counts": (C.c_int32, [_vp, C.c_int64, C.c_int64, _vp, _vp]),
     "lda_to_mallet_packed": (C.c_int32, [_vp, _vp, _i64p, C.POINTER(C.c_int32)]),
     "lda_max_doc_length": (C.c_int32, [_vp, C.POINTER(C.c_int32)]),
     "lda_doc_topic_histograms": (C.c_int32, [_vp, C.c_int32, _i32p, _i32p]),

@@ -224,6 +224,16 @@ constexpr int64_t SCORE_CELLS = int64_t(1) << 22;
 // tokens per chunk (32 MiB of ids; a single longer document goes alone)
 constexpr int64_t HELDOUT_THETA_CELLS = int64_t(1) << 22;
 constexpr int64_t HELDOUT_TOKENS = int64_t(1) << 23;
+// lda_top_words' slab pass: at least TOP_WORDS_SLAB_ROWS rows per slab (a
+// slab's list warms up over its first rows), at most TOP_WORDS_WAVES (slab,
+// topic group) waves, which bounds the slab lists at TOP_WORDS_WAVES * 64 * n
+// keys (32 MiB at n = 64)
+constexpr int64_t TOP_WORDS_SLAB_ROWS = 256;
+constexpr int64_t TOP_WORDS_WAVES = 1024;
+// lda_doc_counts / lda_doc_top_topics: int32 result cells (K or 2 m per
+// document) and documents per chunk
+constexpr int64_t READOUT_CELLS = int64_t(1) << 23;
+constexpr int64_t READOUT_DOCS = int64_t(1) << 20;
 
 }  // namespace
 
@@ -303,6 +313,13 @@ struct lda_ctx {
   int32_t* held_words = nullptr;
   int64_t* held_off = nullptr;
   size_t held_cap[5] = {};
+  // lda_top_words / lda_doc_counts / lda_doc_top_topics: grow-only scratch --
+  // the slab lists [slabs x Kp x n keys], the int32 results of a chunk and
+  // the chunk's document ids
+  unsigned long long* ro_lists = nullptr;
+  int32_t* ro_out = nullptr;
+  int64_t* ro_docs = nullptr;
+  size_t ro_cap[3] = {};
   // 16-bit rows of the snapshot (LDA_SAMPLER_DENSE)
   uint16_t* nw16 = nullptr;
   uint8_t* wide = nullptr;
@@ -450,6 +467,7 @@ struct lda_ctx {
                     (void*)inf_z, (void*)inf_acc, (void*)inf_q, (void*)inf_doff, (void*)inf_range,
                     (void*)score_theta, (void*)score_out, (void*)score_docs,
                     (void*)held_theta, (void*)held_ll, (void*)held_inv, (void*)held_words, (void*)held_off,
+                    (void*)ro_lists, (void*)ro_out, (void*)ro_docs,
                     (void*)perm, (void*)items, (void*)warm.range_doc, (void*)steady.range_doc,
                     (void*)big.tab, (void*)big.tab_m1, (void*)big.F, (void*)big.pfx, (void*)big.scal})
       if (p) (void)hipFree(p);
@@ -2403,6 +2421,145 @@ lda_status lda_score_docs(lda_ctx* c, int32_t metric, int64_t Q, const double* t
     }
   }
   return LDA_OK;
+  });
+}
+
+namespace {
+
+// grow-only readout scratch (lda_ctx::ro_*; capacities in bytes)
+hipError_t ro_need_bytes(lda_ctx* c, void** ptr, size_t bytes, int slot) {
+  if (bytes <= c->ro_cap[slot]) return hipSuccess;
+  if (*ptr) (void)hipFree(*ptr);
+  *ptr = nullptr;
+  c->ro_cap[slot] = 0;
+  const hipError_t e = hipMalloc(ptr, bytes);
+  if (e == hipSuccess) c->ro_cap[slot] = bytes;
+  return e;
+}
+#define ro_need(c, ptr, n, slot) ro_need_bytes((c), reinterpret_cast<void**>(&(ptr)), (n) * sizeof(*(ptr)), (slot))
+
+// the document arguments lda_score_docs takes, checked the same way
+lda_status check_doc_list(const lda_ctx* c, int64_t doc_begin, int64_t M, const int64_t* docs) {
+  if (M < 0) return fail(LDA_ERR_INVALID_ARG, "bad sizes");
+  if (docs) {
+    if (doc_begin != 0) return fail(LDA_ERR_INVALID_ARG, "doc_begin must be 0 with a document list");
+    for (int64_t j = 0; j < M; ++j)
+      if (docs[j] < 0 || docs[j] >= c->D) return fail(LDA_ERR_INVALID_ARG, "document id out of range [0, D)");
+  } else if (doc_begin < 0 || doc_begin > c->D || M > c->D - doc_begin) {
+    return fail(LDA_ERR_INVALID_ARG, "document range out of [0, D)");
+  }
+  return LDA_OK;
+}
+
+// lda_doc_counts (m == 0: rows of K counts) and lda_doc_top_topics (m >= 1:
+// m topics and m counts per document) over chunks of documents
+lda_status doc_readout(lda_ctx* c, int32_t m, int64_t doc_begin, int64_t M, const int64_t* docs, int32_t* out0,
+                       int32_t* out1) {
+  const int32_t K = c->K;
+  const int64_t per_doc = m == 0 ? (int64_t)K : 2 * (int64_t)m;
+  const int64_t Mc = std::min<int64_t>(M, std::min<int64_t>(READOUT_DOCS, std::max<int64_t>(1, READOUT_CELLS / per_doc)));
+  double A = 0.0;
+  for (int k = 0; k < K; ++k) A += c->alpha[(size_t)k];
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(ro_need(c, c->ro_out, (size_t)(Mc * per_doc), 1));
+  if (docs) HIP_TRY(ro_need(c, c->ro_docs, (size_t)Mc, 2));
+  const int wave_blocks = c->cus * 8;
+  for (int64_t j0 = 0; j0 < M; j0 += Mc) {
+    const int64_t mn = std::min<int64_t>(Mc, M - j0);
+    if (docs)
+      HIP_TRY(hipMemcpyAsync(c->ro_docs, docs + j0, sizeof(int64_t) * (size_t)mn, hipMemcpyHostToDevice, c->stream));
+    lda::DocReadoutArgs a{};
+    a.z = c->z;
+    a.doc_off = c->doc_off;
+    a.docs = docs ? c->ro_docs : nullptr;
+    a.doc_begin = doc_begin + j0;
+    a.M = mn;
+    a.alpha = c->alpha_d;
+    a.A = A;
+    a.K = K;
+    a.Kp = c->Kp;
+    a.m = m;
+    a.topics = c->ro_out;
+    a.counts = c->ro_out + (size_t)mn * (size_t)m;
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((mn + 3) / 4, wave_blocks));
+    if (m == 0) {
+      HIP_TRY(lda::launch_doc_counts(a, blocks, c->stream));
+      HIP_TRY(hipMemcpyAsync(out0 + (size_t)j0 * K, c->ro_out, sizeof(int32_t) * (size_t)mn * K, hipMemcpyDeviceToHost,
+                             c->stream));
+    } else {
+      HIP_TRY(lda::launch_doc_top_topics(a, blocks, c->stream));
+      HIP_TRY(hipMemcpyAsync(out0 + (size_t)j0 * m, a.topics, sizeof(int32_t) * (size_t)mn * m, hipMemcpyDeviceToHost,
+                             c->stream));
+      HIP_TRY(hipMemcpyAsync(out1 + (size_t)j0 * m, a.counts, sizeof(int32_t) * (size_t)mn * m, hipMemcpyDeviceToHost,
+                             c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));   // the scratch is reused by the next chunk
+  }
+  return LDA_OK;
+}
+
+}  // namespace
+
+lda_status lda_top_words(lda_ctx* c, int32_t n, int32_t* word_ids, int32_t* counts) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (n < 1 || n > LDA_TOP_WORDS_MAX) return fail(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_TOP_WORDS_MAX]");
+  if (!word_ids || !counts) return fail(LDA_ERR_INVALID_ARG, "null output");
+  if (c->pending) return fail(LDA_ERR_STATE, "top words with a pending delta: call lda_apply first");
+  const size_t cells = (size_t)c->K * (size_t)n;
+  if (c->V == 0) {
+    std::fill(word_ids, word_ids + cells, -1);
+    std::fill(counts, counts + cells, 0);
+    return LDA_OK;
+  }
+  const int64_t G = c->Kp / 64;
+  int64_t slabs = std::min<int64_t>((c->V + TOP_WORDS_SLAB_ROWS - 1) / TOP_WORDS_SLAB_ROWS,
+                                    std::max<int64_t>(1, TOP_WORDS_WAVES / G));
+  const int64_t slab_rows = (c->V + slabs - 1) / slabs;
+  slabs = (c->V + slab_rows - 1) / slab_rows;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(ro_need(c, c->ro_lists, (size_t)(slabs * c->Kp) * (size_t)n, 0));
+  HIP_TRY(ro_need(c, c->ro_out, 2 * cells, 1));
+  lda::TopWordsArgs a{};
+  a.nw = c->nw;
+  a.V = c->V;
+  a.K = c->K;
+  a.Kp = c->Kp;
+  a.n = n;
+  a.slabs = (int32_t)slabs;
+  a.slab_rows = (int32_t)slab_rows;
+  a.lists = c->ro_lists;
+  a.ids = c->ro_out;
+  a.counts = c->ro_out + cells;
+  HIP_TRY(lda::launch_top_words(a, c->stream));
+  HIP_TRY(hipMemcpyAsync(word_ids, a.ids, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(counts, a.counts, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LDA_OK;
+  });
+}
+
+lda_status lda_doc_counts(lda_ctx* c, int64_t doc_begin, int64_t M, const int64_t* docs, int32_t* nd) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (c->pending) return fail(LDA_ERR_STATE, "document counts with a pending delta: call lda_apply first");
+  if (lda_status s = check_doc_list(c, doc_begin, M, docs); s != LDA_OK) return s;
+  if (M == 0) return LDA_OK;
+  if (!nd) return fail(LDA_ERR_INVALID_ARG, "null output");
+  return doc_readout(c, 0, doc_begin, M, docs, nd, nullptr);
+  });
+}
+
+lda_status lda_doc_top_topics(lda_ctx* c, int32_t m, int64_t doc_begin, int64_t M, const int64_t* docs,
+                              int32_t* topics, int32_t* counts) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (m < 1 || m > LDA_TOP_TOPICS_MAX) return fail(LDA_ERR_INVALID_ARG, "m must be in [1, LDA_TOP_TOPICS_MAX]");
+  if (c->pending) return fail(LDA_ERR_STATE, "top topics with a pending delta: call lda_apply first");
+  if (lda_status s = check_doc_list(c, doc_begin, M, docs); s != LDA_OK) return s;
+  if (M == 0) return LDA_OK;
+  if (!topics || !counts) return fail(LDA_ERR_INVALID_ARG, "null output");
+  return doc_readout(c, m, doc_begin, M, docs, topics, counts);
   });
 }
 

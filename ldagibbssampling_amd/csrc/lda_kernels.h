@@ -238,6 +238,36 @@ struct DocScoreArgs {
   int64_t ldo;
 };
 hipError_t launch_doc_scores(const DocScoreArgs& a, int blocks, hipStream_t st);
+// lda_top_words: stage 1 (k_top_words_slab) keeps, per (slab of rows, topic),
+// the slab's best n keys (count << 32 | 0xFFFFFFFF - word) as a descending
+// list, lists[((slab * G + group) * n + i) * 64 + lane] (G = Kp / 64, empty
+// slots 0); stage 2 (k_top_words_merge) merges a topic's slab lists into
+// ids / counts [K * n].  slabs <= TOP_WORDS_MAX_SLABS.
+constexpr int TOP_WORDS_MAX_SLABS = 1024;
+struct TopWordsArgs {
+  const int32_t* nw;             // [V * Kp]
+  int32_t V, K, Kp, n;
+  int32_t slabs, slab_rows;      // slab s holds rows [s * slab_rows, min(V, (s + 1) * slab_rows))
+  unsigned long long* lists;     // [slabs * Kp * n]
+  int32_t* ids;                  // [K * n]
+  int32_t* counts;               // [K * n]
+};
+hipError_t launch_top_words(const TopWordsArgs& a, hipStream_t st);
+// lda_doc_counts (k_doc_counts) and lda_doc_top_topics (k_doc_top_topics): M
+// listed documents of the shard, one wave per document
+struct DocReadoutArgs {
+  const int32_t* z;
+  const int64_t* doc_off;
+  const int64_t* docs;      // [M] shard-local document ids, or null: doc_begin + j
+  int64_t doc_begin, M;
+  const double* alpha;      // [K]
+  double A;                 // alpha[0] + ... + alpha[K-1], added in that order
+  int32_t K, Kp, m;
+  int32_t* topics;          // k_doc_top_topics: [M * m]; k_doc_counts: the rows [M * K]
+  int32_t* counts;          // k_doc_top_topics: [M * m]
+};
+hipError_t launch_doc_counts(const DocReadoutArgs& a, int blocks, hipStream_t st);
+hipError_t launch_doc_top_topics(const DocReadoutArgs& a, int blocks, hipStream_t st);
 // lda_heldout_loglik (k_doc_completion): the scored tokens of Dh held-out
 // documents against the int32 nw rows.  A wave takes a document's tokens in
 // batches of doc_completion_batch(C): 64 up to C = 8, 16 above (the batch's

@@ -3201,6 +3201,191 @@ __global__ __launch_bounds__(256) void k_doc_scores(const DocScoreArgs a) {
   }
 }
 
+// The largest of a 64-bit value over the wave (every lane gets it).
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t hi = (uint32_t)__shfl_xor((int)(v >> 32), o), lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o);
+    const unsigned long long other = ((unsigned long long)hi << 32) | lo;
+    v = other > v ? other : v;
+  }
+  return v;
+}
+
+// lda_top_words, stage 1: one wave per (slab of rows, group of 64 topics),
+// lane l owning topic group * 64 + l, so a row's segment is one coalesced
+// 256-byte load.  key = count << 32 | (0xFFFFFFFF - word) is unique per topic
+// and its descending order is count descending, then word ascending; a cell
+// with count 0 has no key (0 = an empty slot).  The lane's best n keys are a
+// descending list in its own LDS column list[i * 64 + lane] (no lane reads
+// another's column: no fence), the smallest of them (thr) in a register: a
+// row that does not beat thr costs one compare, one that does is inserted by
+// shifting the tail.  Rows are loaded eight at a time to keep loads in flight.
+// Integer only; the slab's list is a function of the slab's rows alone.
+__global__ __launch_bounds__(64) void k_top_words_slab(const TopWordsArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long tw_list[];   // [n][64]
+  const int lane = threadIdx.x, n = a.n;
+  const int s = blockIdx.x, g = blockIdx.y, G = a.Kp >> 6;
+  for (int i = 0; i < n; ++i) tw_list[i * 64 + lane] = 0;
+  unsigned long long thr = 0;
+  const int32_t* __restrict__ col = a.nw + (size_t)g * 64 + lane;
+  const int64_t w0 = (int64_t)s * a.slab_rows, w1 = min((int64_t)a.V, w0 + a.slab_rows);
+  for (int64_t w = w0; w < w1; w += 8) {
+    int32_t c[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) c[u] = w + u < w1 ? col[(size_t)(w + u) * a.Kp] : 0;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const unsigned long long key =
+          ((unsigned long long)(uint32_t)c[u] << 32) | (0xFFFFFFFFu - (uint32_t)(w + u));
+      if (c[u] > 0 && key > thr) {
+        int i = n - 1;
+        while (i > 0) {
+          const unsigned long long prev = tw_list[(i - 1) * 64 + lane];
+          if (prev >= key) break;
+          tw_list[i * 64 + lane] = prev;
+          --i;
+        }
+        tw_list[i * 64 + lane] = key;
+        thr = tw_list[(n - 1) * 64 + lane];
+      }
+    }
+  }
+  unsigned long long* __restrict__ out = a.lists + ((size_t)s * G + g) * n * 64 + lane;
+  for (int i = 0; i < n; ++i) out[(size_t)i * 64] = tw_list[i * 64 + lane];
+}
+
+// lda_top_words, stage 2: one wave per topic k < K merges the topic's slab
+// lists.  Lane l holds the heads of slabs l, l + 64, ... (head / ptr in LDS,
+// each entry touched by its own lane only); n rounds of a wave-wide maximum
+// over the heads -- the keys are unique, so the maximum names its slab --
+// whose owner steps that slab's list.  An exhausted merge (maximum 0) fills
+// id -1, count 0.
+__global__ __launch_bounds__(64) void k_top_words_merge(const TopWordsArgs a) {
+  __shared__ unsigned long long head[TOP_WORDS_MAX_SLABS];
+  __shared__ int32_t ptr[TOP_WORDS_MAX_SLABS];
+  const int lane = threadIdx.x, n = a.n, k = blockIdx.x, g = k >> 6, kl = k & 63, G = a.Kp >> 6;
+  const unsigned long long* __restrict__ lists = a.lists;
+  auto at = [&](int s, int i) { return lists[(((size_t)s * G + g) * n + i) * 64 + kl]; };
+  for (int s = lane; s < a.slabs; s += 64) {
+    head[s] = at(s, 0);
+    ptr[s] = 0;
+  }
+  for (int i = 0; i < n; ++i) {
+    unsigned long long best = 0;
+    int bs = -1;
+    for (int s = lane; s < a.slabs; s += 64) {
+      const unsigned long long h = head[s];
+      if (h > best) {
+        best = h;
+        bs = s;
+      }
+    }
+    const unsigned long long mx = wave_max_u64(best);
+    if (mx != 0 && best == mx) {
+      const int p = ++ptr[bs];
+      head[bs] = p < n ? at(bs, p) : 0ull;
+    }
+    if (lane == 0) {
+      a.ids[(size_t)k * n + i] = mx != 0 ? (int32_t)(0xFFFFFFFFu - (uint32_t)mx) : -1;
+      a.counts[(size_t)k * n + i] = (int32_t)(mx >> 32);
+    }
+  }
+}
+
+// lda_doc_counts: the dense nd rows of the listed documents (k_doc_topics
+// with a document list), one wave per document.
+__global__ __launch_bounds__(256) void k_doc_counts(const DocReadoutArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int32_t h[];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  int32_t* hist = h + wid * a.Kp;
+  for (int i = lane; i < a.Kp; i += 64) hist[i] = 0;
+  wave_lds_fence();
+  const int32_t* __restrict__ z = a.z;
+  for (int64_t j = (int64_t)blockIdx.x * 4 + wid; j < a.M; j += (int64_t)gridDim.x * 4) {
+    const int64_t d = a.docs ? a.docs[j] : a.doc_begin + j;
+    for (int64_t i = a.doc_off[d] + lane; i < a.doc_off[d + 1]; i += 64) atomicAdd(&hist[z[i]], 1);
+    wave_lds_fence();
+    for (int k = lane; k < a.K; k += 64) a.topics[j * a.K + k] = hist[k];
+    for (int k = lane; k < a.Kp; k += 64) hist[k] = 0;
+    wave_lds_fence();
+  }
+}
+
+// lda_doc_top_topics: the m topics of each listed document with the largest
+// weight (alpha_k + n_dk) / (n_d + A), fp64, the host's expression
+// (ParallelTopicModel::documentTopics); equal weights by ascending topic.
+// One wave per document, the counts in the per-wave LDS histogram; lane l
+// owns topics [l C, (l + 1) C) and keeps its best remaining topic (bits of
+// the weight, id).  The weights are positive doubles, so their bit patterns
+// order as unsigned integers.  m rounds of a wave-wide arg-max (larger bits,
+// then smaller id); the winner's owner writes the slot, retires the topic
+// (its histogram cell becomes -1) and rescans its own C topics.  With every
+// topic retired (m > K) the slots fill with -1 / 0.
+__global__ __launch_bounds__(256) void k_doc_top_topics(const DocReadoutArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int32_t h[];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  int32_t* hist = h + wid * a.Kp;
+  for (int i = lane; i < a.Kp; i += 64) hist[i] = 0;
+  wave_lds_fence();
+  const int32_t* __restrict__ z = a.z;
+  const double* __restrict__ alpha = a.alpha;
+  const int C = a.Kp >> 6, base = lane * C, m = a.m;
+  for (int64_t j = (int64_t)blockIdx.x * 4 + wid; j < a.M; j += (int64_t)gridDim.x * 4) {
+    const int64_t d = a.docs ? a.docs[j] : a.doc_begin + j;
+    const int64_t t0 = a.doc_off[d], t1 = a.doc_off[d + 1];
+    for (int64_t i = t0 + lane; i < t1; i += 64) atomicAdd(&hist[z[i]], 1);
+    wave_lds_fence();
+    const double S = (double)(t1 - t0) + a.A;
+    unsigned long long bits;
+    int id;
+    auto scan = [&]() {
+      bits = 0;
+      id = INT32_MAX;
+      for (int c = 0; c < C; ++c) {
+        const int k = base + c;
+        if (k >= a.K) break;
+        const int32_t cnt = hist[k];
+        if (cnt < 0) continue;
+        const unsigned long long b = (unsigned long long)__double_as_longlong((alpha[k] + (double)cnt) / S);
+        if (b > bits) {   // ascending k: the smallest id of equal weights stays
+          bits = b;
+          id = k;
+        }
+      }
+    };
+    scan();
+    for (int i = 0; i < m; ++i) {
+      unsigned long long wb = bits;
+      int wi = id;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t hi = (uint32_t)__shfl_xor((int)(wb >> 32), o), lo = (uint32_t)__shfl_xor((int)(uint32_t)wb, o);
+        const unsigned long long ob = ((unsigned long long)hi << 32) | lo;
+        const int oi = __shfl_xor(wi, o);
+        if (ob > wb || (ob == wb && oi < wi)) {
+          wb = ob;
+          wi = oi;
+        }
+      }
+      if (wb == 0) {
+        if (lane == 0) {
+          a.topics[j * m + i] = -1;
+          a.counts[j * m + i] = 0;
+        }
+      } else if (id == wi) {   // this lane owns the winner
+        a.topics[j * m + i] = wi;
+        a.counts[j * m + i] = hist[wi];
+        hist[wi] = -1;
+        scan();
+      }
+    }
+    wave_lds_fence();
+    for (int k = lane; k < a.Kp; k += 64) hist[k] = 0;
+    wave_lds_fence();
+  }
+}
+
 // lda_heldout_loglik: inv[k] = 1 / (nwsum[k] + V beta) in fp64, 0 for the
 // padded topics.
 __global__ __launch_bounds__(256) void k_heldout_inv(const int32_t* __restrict__ nwsum, double vbeta, int32_t K,
@@ -4014,6 +4199,32 @@ hipError_t launch_doc_scores(const DocScoreArgs& a, int blocks, hipStream_t st) 
     hipLaunchKernelGGL(k_doc_scores<DOC_SCORE_TILE_SMALL>, dim3(blocks), dim3(256), lds, st, a);
   else
     hipLaunchKernelGGL(k_doc_scores<DOC_SCORE_TILE>, dim3(blocks), dim3(256), lds, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_top_words(const TopWordsArgs& a, hipStream_t st) {
+  if (a.n < 1 || a.n > 64 || a.slabs < 1 || a.slabs > TOP_WORDS_MAX_SLABS || a.V < 1 ||
+      (int64_t)a.slabs * a.slab_rows < a.V)
+    return hipErrorInvalidValue;
+  // 512 n bytes of LDS per one-wave block: 32 KiB at n = 64
+  hipLaunchKernelGGL(k_top_words_slab, dim3(a.slabs, a.Kp / 64), dim3(64),
+                     (size_t)a.n * 64 * sizeof(unsigned long long), st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_top_words_merge, dim3(a.K), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_doc_counts(const DocReadoutArgs& a, int blocks, hipStream_t st) {
+  if (a.M <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_doc_counts, dim3(blocks), dim3(256), 4 * (size_t)a.Kp * sizeof(int32_t), st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_doc_top_topics(const DocReadoutArgs& a, int blocks, hipStream_t st) {
+  if (a.M <= 0) return hipSuccess;
+  if (a.m < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_doc_top_topics, dim3(blocks), dim3(256), 4 * (size_t)a.Kp * sizeof(int32_t), st, a);
   return hipGetLastError();
 }
 

@@ -888,7 +888,9 @@ void ParallelTopicModel::estimate() {
   for (int32_t it = 1; it <= num_iterations_; ++it) {
     if (show_before(it)) {
       collect_ll();
-      log("\n" + displayTopWords(words_per_topic_, false));
+      // log() discards the text when silent: do not compute it then (the
+      // sweeps are batched the same way either way)
+      if (verbosity_ > 0) log("\n" + displayTopWords(words_per_topic_, false));
     }
     int32_t last = it;
     while (last < num_iterations_ && !work_after(last) && !show_before(last + 1)) ++last;
@@ -946,12 +948,80 @@ void ParallelTopicModel::estimate() {
   for (auto c : shards_->ctx) check(lda_synchronize(c), "lda_synchronize");
 }
 
+void ParallelTopicModel::topWords(int32_t n, int32_t* word_ids, int32_t* counts) {
+  if (n < 1 || n > LDA_TOP_WORDS_MAX) raise(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_TOP_WORDS_MAX]");
+  if (!word_ids || !counts) raise(LDA_ERR_INVALID_ARG, "null output");
+  ensureShards();
+  check(lda_top_words(shards_->ctx[0], n, word_ids, counts), "lda_top_words");
+}
+
+void ParallelTopicModel::docReadout(int32_t mtop, int64_t M, const int64_t* docs, int32_t* out0, int32_t* out1) {
+  if (M < 0) raise(LDA_ERR_INVALID_ARG, "bad sizes");
+  const int64_t D = numDocs();
+  if (!docs && M != D) raise(LDA_ERR_INVALID_ARG, "without a document list M must be the number of documents");
+  for (int64_t j = 0; docs && j < M; ++j)
+    if (docs[j] < 0 || docs[j] >= D) raise(LDA_ERR_INVALID_ARG, "document id out of range [0, D)");
+  if (M == 0) return;
+  if (!out0 || (mtop > 0 && !out1)) raise(LDA_ERR_INVALID_ARG, "null output");
+  ensureShards();
+  const int64_t width = mtop > 0 ? mtop : K_;
+  auto call = [&](size_t g, int64_t m, const int64_t* local, int32_t* o0, int32_t* o1) {
+    if (mtop > 0)
+      check(lda_doc_top_topics(shards_->ctx[g], mtop, 0, m, local, o0, o1), "lda_doc_top_topics");
+    else
+      check(lda_doc_counts(shards_->ctx[g], 0, m, local, o0), "lda_doc_counts");
+  };
+  const std::vector<int64_t>& begin = shards_->doc_begin;
+  const size_t G = shards_->ctx.size();
+  if (!docs) {
+    // the shards' document ranges are consecutive: each writes its own rows
+    for (size_t g = 0; g < G; ++g) {
+      const int64_t d0 = begin[g], m = begin[g + 1] - d0;
+      if (m > 0) call(g, m, nullptr, out0 + d0 * width, out1 ? out1 + d0 * width : nullptr);
+    }
+    return;
+  }
+  if (G == 1) {
+    call(0, M, docs, out0, out1);
+    return;
+  }
+  std::vector<std::vector<int64_t>> local(G), pos(G);
+  for (int64_t j = 0; j < M; ++j) {
+    const size_t g = (size_t)(std::upper_bound(begin.begin(), begin.end(), docs[j]) - begin.begin()) - 1;
+    local[g].push_back(docs[j] - begin[g]);
+    pos[g].push_back(j);
+  }
+  std::vector<int32_t> p0, p1;
+  for (size_t g = 0; g < G; ++g) {
+    const int64_t m = (int64_t)local[g].size();
+    if (m == 0) continue;
+    p0.resize((size_t)(m * width));
+    if (mtop > 0) p1.resize((size_t)(m * width));
+    call(g, m, local[g].data(), p0.data(), p1.data());
+    for (int64_t i = 0; i < m; ++i) {
+      const int64_t j = pos[g][(size_t)i];
+      std::copy(p0.begin() + i * width, p0.begin() + (i + 1) * width, out0 + j * width);
+      if (mtop > 0) std::copy(p1.begin() + i * width, p1.begin() + (i + 1) * width, out1 + j * width);
+    }
+  }
+}
+
+void ParallelTopicModel::docTopTopics(int32_t mtop, int64_t M, const int64_t* docs, int32_t* topics,
+                                      int32_t* counts) {
+  if (mtop < 1 || mtop > LDA_TOP_TOPICS_MAX) raise(LDA_ERR_INVALID_ARG, "m must be in [1, LDA_TOP_TOPICS_MAX]");
+  docReadout(mtop, M, docs, topics, counts);
+}
+
+void ParallelTopicModel::docCounts(int64_t M, const int64_t* docs, int32_t* nd) { docReadout(0, M, docs, nd, nullptr); }
+
 std::vector<double> ParallelTopicModel::getTopicProbabilities(int64_t doc) {
   if (doc < 0 || doc >= numDocs()) raise(LDA_ERR_INVALID_ARG, "document index out of range");
-  ensureShards();
-  const std::vector<int32_t> z = topics();
+  // the document's counts from the device (no copy of z); the arithmetic,
+  // the sequential sum included, is unchanged
+  std::vector<int32_t> nd((size_t)K_);
+  docCounts(1, &doc, nd.data());
   std::vector<double> dist((size_t)K_, 0.0);
-  for (int64_t i = doc_off_[doc]; i < doc_off_[doc + 1]; ++i) dist[(size_t)z[(size_t)i]] += 1.0;
+  for (int k = 0; k < K_; ++k) dist[(size_t)k] = (double)nd[(size_t)k];
   double sum = 0.0;
   for (int k = 0; k < K_; ++k) {
     dist[(size_t)k] += alpha_[(size_t)k];
@@ -969,44 +1039,115 @@ static void sort_ids(std::vector<std::pair<int32_t, double>>& v) {
 
 std::string ParallelTopicModel::documentTopics(double threshold, int32_t max) {
   ensureShards();
-  const std::vector<int32_t> z = topics();
   if (max < 0 || max > K_) max = K_;
+  const int64_t D = numDocs();
   std::string out = "#doc source topic proportion ...\n";
-  std::vector<int32_t> cnt((size_t)K_);
-  std::vector<std::pair<int32_t, double>> sorted((size_t)K_);
-  for (int64_t d = 0; d < numDocs(); ++d) {
+  auto head = [&](int64_t d) {
     out += std::to_string(d);
     out += ' ';
     out += has_source_[(size_t)d] ? sources_[(size_t)d] : std::string("null-source");
     out += ' ';
-    std::fill(cnt.begin(), cnt.end(), 0);
-    const int64_t len = doc_off_[d + 1] - doc_off_[d];
-    for (int64_t i = doc_off_[d]; i < doc_off_[d + 1]; ++i) cnt[(size_t)z[(size_t)i]]++;
-    for (int k = 0; k < K_; ++k)
-      sorted[(size_t)k] = {k, (alpha_[(size_t)k] + cnt[(size_t)k]) / ((double)len + alpha_sum_)};
-    sort_ids(sorted);
-    for (int i = 0; i < max; ++i) {
-      if (sorted[(size_t)i].second < threshold) break;
-      out += std::to_string(sorted[(size_t)i].first) + " " + java_double(sorted[(size_t)i].second) + " ";
+  };
+  auto weight = [&](int k, int32_t cnt, int64_t len) {
+    return (alpha_[(size_t)k] + cnt) / ((double)len + alpha_sum_);
+  };
+  // The device orders by the same expression with alphaSum = the sum of alpha
+  // added in index order.  That is this model's order when alpha_sum_ holds
+  // those bits (the constructor's alphaSum / K * K may not), or when alpha is
+  // uniform: the numerators are then alpha + an integer, equal or at least 1
+  // apart, and their order does not depend on the denominator's last bits.
+  double seq_sum = 0.0;
+  bool uniform = true;
+  for (int k = 0; k < K_; ++k) {
+    seq_sum += alpha_[(size_t)k];
+    uniform = uniform && alpha_[(size_t)k] == alpha_[0];
+  }
+  const bool device_order = max >= 1 && max <= LDA_TOP_TOPICS_MAX && (uniform || seq_sum == alpha_sum_);
+  if (device_order) {
+    // the order from the device, a chunk of documents at a time; the weights
+    // are recomputed here from the returned counts, so the text is the same
+    const int64_t chunk = std::max<int64_t>(1, (int64_t(1) << 20) / max);
+    std::vector<int32_t> top, cnt;
+    std::vector<int64_t> ids;
+    for (int64_t d0 = 0; d0 < D; d0 += chunk) {
+      const int64_t m = std::min(chunk, D - d0);
+      top.resize((size_t)(m * max));
+      cnt.resize((size_t)(m * max));
+      ids.resize((size_t)m);
+      std::iota(ids.begin(), ids.end(), d0);
+      docTopTopics(max, m, D == m ? nullptr : ids.data(), top.data(), cnt.data());
+      for (int64_t d = d0; d < d0 + m; ++d) {
+        head(d);
+        const int64_t len = doc_off_[d + 1] - doc_off_[d];
+        for (int i = 0; i < max; ++i) {
+          const size_t at = (size_t)((d - d0) * max + i);
+          const double w = weight(top[at], cnt[at], len);
+          if (w < threshold) break;
+          out += std::to_string(top[at]) + " " + java_double(w) + " ";
+        }
+        out += " \n";
+      }
     }
-    out += " \n";
+    return out;
+  }
+  // every topic (or more than the device selects): the documents' count rows
+  // from the device in bounded chunks, sorted here
+  const int64_t chunk = std::max<int64_t>(1, (int64_t(1) << 22) / K_);
+  std::vector<int32_t> nd;
+  std::vector<int64_t> ids;
+  std::vector<std::pair<int32_t, double>> sorted((size_t)K_);
+  for (int64_t d0 = 0; d0 < D; d0 += chunk) {
+    const int64_t m = std::min(chunk, D - d0);
+    nd.resize((size_t)(m * K_));
+    ids.resize((size_t)m);
+    std::iota(ids.begin(), ids.end(), d0);
+    docCounts(m, D == m ? nullptr : ids.data(), nd.data());
+    for (int64_t d = d0; d < d0 + m; ++d) {
+      head(d);
+      const int64_t len = doc_off_[d + 1] - doc_off_[d];
+      const int32_t* cnt = nd.data() + (size_t)((d - d0) * K_);
+      for (int k = 0; k < K_; ++k) sorted[(size_t)k] = {k, weight(k, cnt[k], len)};
+      sort_ids(sorted);
+      for (int i = 0; i < max; ++i) {
+        if (sorted[(size_t)i].second < threshold) break;
+        out += std::to_string(sorted[(size_t)i].first) + " " + java_double(sorted[(size_t)i].second) + " ";
+      }
+      out += " \n";
+    }
   }
   return out;
 }
 
 std::string ParallelTopicModel::displayTopWords(int32_t num_words, bool using_new_lines) {
   ensureShards();
-  std::vector<int32_t> nw((size_t)V_ * K_);
-  check(lda_get_counts(shards_->ctx[0], nw.data(), nullptr, nullptr, nullptr), "lda_get_counts");
+  // Mallet prints numWords - 1 words: up to LDA_TOP_WORDS_MAX of them are
+  // selected on the device (K x n ids and counts come back); more than that
+  // take the whole table to the host as before
+  const int32_t n_dev = num_words - 1;
+  const bool device = n_dev >= 1 && n_dev <= LDA_TOP_WORDS_MAX;
+  std::vector<int32_t> nw, top_ids, top_counts;
+  if (device) {
+    top_ids.resize((size_t)K_ * n_dev);
+    top_counts.resize((size_t)K_ * n_dev);
+    topWords(n_dev, top_ids.data(), top_counts.data());
+  } else if (n_dev >= 1) {
+    nw.resize((size_t)V_ * K_);
+    check(lda_get_counts(shards_->ctx[0], nw.data(), nullptr, nullptr, nullptr), "lda_get_counts");
+  }
   std::string out;
   std::vector<std::pair<int32_t, double>> words;
   for (int k = 0; k < K_; ++k) {
     words.clear();
-    for (int32_t w = 0; w < V_; ++w) {
-      const int32_t c = nw[(size_t)w * K_ + k];
-      if (c > 0) words.emplace_back(w, (double)c);
+    if (device) {
+      for (int32_t i = 0; i < n_dev && top_ids[(size_t)k * n_dev + i] >= 0; ++i)
+        words.emplace_back(top_ids[(size_t)k * n_dev + i], (double)top_counts[(size_t)k * n_dev + i]);
+    } else if (n_dev >= 1) {
+      for (int32_t w = 0; w < V_; ++w) {
+        const int32_t c = nw[(size_t)w * K_ + k];
+        if (c > 0) words.emplace_back(w, (double)c);
+      }
+      sort_ids(words);
     }
-    sort_ids(words);
     auto name = [&](int32_t w) { return alphabet_.empty() ? std::to_string(w) : alphabet_[(size_t)w]; };
     // Mallet's loop starts its word counter at 1 and stops before numWords
     const size_t n = (size_t)std::max(0, std::min<int32_t>(num_words - 1, (int32_t)words.size()));
@@ -1637,6 +1778,22 @@ lda_status ldatm_get_topic_probabilities(ldatm* m, int64_t doc, double* out) {
     const std::vector<double> p = m->model.getTopicProbabilities(doc);
     std::copy(p.begin(), p.end(), out);
   });
+}
+
+lda_status ldatm_top_words(ldatm* m, int32_t n, int32_t* word_ids, int32_t* counts) {
+  TM_CHECK(m);
+  return guard([&] { m->model.topWords(n, word_ids, counts); });
+}
+
+lda_status ldatm_doc_top_topics(ldatm* m, int32_t mtop, int64_t M, const int64_t* docs, int32_t* topics,
+                                int32_t* counts) {
+  TM_CHECK(m);
+  return guard([&] { m->model.docTopTopics(mtop, M, docs, topics, counts); });
+}
+
+lda_status ldatm_doc_counts(ldatm* m, int64_t M, const int64_t* docs, int32_t* nd) {
+  TM_CHECK(m);
+  return guard([&] { m->model.docCounts(M, docs, nd); });
 }
 
 lda_status ldatm_document_topics_text(ldatm* m, double threshold, int32_t max, char* buf, size_t cap,

@@ -98,6 +98,18 @@ class ParallelTopicModel {
   void counts(int32_t* nw, int32_t* nwsum);           // nw[V*K] (nullable), nwsum[K]
   std::vector<double> getTopicProbabilities(int64_t doc);
 
+  // ---- readouts selected on the device -----------------
+  // lda_top_words on shard 0 (every shard holds the same global counts):
+  // word_ids / counts [K*n], count descending, ties by ascending word id,
+  // -1 / 0 past a topic's last nonzero word
+  void topWords(int32_t n, int32_t* word_ids, int32_t* counts);
+  // the global document ids docs[M] (null: every document, M = numDocs())
+  // mapped onto the shards as scoreTheta maps them; each shard answers for
+  // its own documents (lda_doc_top_topics / lda_doc_counts) and the rows are
+  // scattered back into the caller's order.  topics / counts [M*mtop]; nd [M*K]
+  void docTopTopics(int32_t mtop, int64_t M, const int64_t* docs, int32_t* topics, int32_t* counts);
+  void docCounts(int64_t M, const int64_t* docs, int32_t* nd);
+
   // ---- outputs -------------------------------------------------------
   std::string documentTopics(double threshold, int32_t max);
   std::string displayTopWords(int32_t num_words, bool using_new_lines);
@@ -153,6 +165,8 @@ class ParallelTopicModel {
   // alpha statistics in one lda_hyper_statistics call
   void optimizeBeta(const std::vector<int32_t>& count_hist, const std::vector<int32_t>& nwsum);
   void log(const std::string& line) const;
+  // docTopTopics (mtop >= 1) / docCounts (mtop == 0, width K) over the shards
+  void docReadout(int32_t mtop, int64_t M, const int64_t* docs, int32_t* out0, int32_t* out1);
 
   int32_t K_;
   double alpha_sum_, beta_;

@@ -386,6 +386,53 @@ class GibbsSampler:
                                           scores.ctypes.data), "lda_score_docs")
         return scores
 
+    def _doc_list(self, docs, doc_begin, num_docs):
+        """(begin, M, ids or None) of a document argument as score_docs takes it."""
+        if docs is not None:
+            ids = np.ascontiguousarray(docs, dtype=np.int64).reshape(-1)
+            return 0, len(ids), ids
+        begin = int(doc_begin)
+        return begin, (self.D - begin if num_docs is None else int(num_docs)), None
+
+    def top_words(self, n: int):
+        """lda_top_words: per topic the n words with the largest count (count
+        descending, equal counts by ascending word id), selected on the device.
+        Returns (word_ids[K, n], counts[K, n]) int32; slots past a topic's last
+        nonzero word hold -1 / 0."""
+        n = int(n)
+        if not 1 <= n <= capi.TOP_WORDS_MAX:
+            raise ValueError(f"n must be in [1, {capi.TOP_WORDS_MAX}]")
+        ids = np.zeros((self.K, n), dtype=np.int32)
+        cnt = np.zeros((self.K, n), dtype=np.int32)
+        capi.check(self._L.lda_top_words(self._h, n, ids.ctypes.data, cnt.ctypes.data), "lda_top_words")
+        return ids, cnt
+
+    def doc_top_topics(self, m: int, docs=None, doc_begin: int = 0, num_docs: int | None = None):
+        """lda_doc_top_topics: the m topics of each listed document with the
+        largest weight (alpha_k + n_dk) / (n_d + alphaSum), equal weights by
+        ascending topic id, selected on the device from z.  docs as score_docs
+        takes them.  Returns (topics[M, m], counts[M, m]) int32; slots past K
+        hold -1 / 0."""
+        m = int(m)
+        if not 1 <= m <= capi.TOP_TOPICS_MAX:
+            raise ValueError(f"m must be in [1, {capi.TOP_TOPICS_MAX}]")
+        begin, M, ids = self._doc_list(docs, doc_begin, num_docs)
+        topics = np.zeros((max(M, 0), m), dtype=np.int32)
+        cnt = np.zeros((max(M, 0), m), dtype=np.int32)
+        capi.check(self._L.lda_doc_top_topics(self._h, m, begin, M, ids.ctypes.data if ids is not None and M else None,
+                                              topics.ctypes.data, cnt.ctypes.data), "lda_doc_top_topics")
+        return topics, cnt
+
+    def doc_counts(self, docs=None, doc_begin: int = 0, num_docs: int | None = None) -> np.ndarray:
+        """lda_doc_counts: the topic counts nd[M, K] (int32) of the listed
+        documents from the current z on the device; docs as score_docs takes
+        them."""
+        begin, M, ids = self._doc_list(docs, doc_begin, num_docs)
+        nd = np.zeros((max(M, 0), self.K), dtype=np.int32)
+        capi.check(self._L.lda_doc_counts(self._h, begin, M, ids.ctypes.data if ids is not None and M else None,
+                                          nd.ctypes.data), "lda_doc_counts")
+        return nd
+
     def heldout_loglik(self, theta, doc_off, words):
         """lda_heldout_loglik: the log likelihood of the scored tokens of Dh
         held-out documents (doc_off[Dh + 1], words) under their topic

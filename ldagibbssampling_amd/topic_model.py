@@ -72,6 +72,9 @@ TM_SIGNATURES = {
     "ldatm_get_z": (_i32, [_vp, _i32p]),
     "ldatm_get_counts": (_i32, [_vp, _vp, _vp]),
     "ldatm_get_topic_probabilities": (_i32, [_vp, C.c_int64, _f64p]),
+    "ldatm_top_words": (_i32, [_vp, _i32, _vp, _vp]),
+    "ldatm_doc_top_topics": (_i32, [_vp, _i32, C.c_int64, _vp, _vp, _vp]),
+    "ldatm_doc_counts": (_i32, [_vp, C.c_int64, _vp, _vp]),
     "ldatm_print_document_topics": (_i32, [_vp, C.c_char_p, C.c_double, _i32]),
     "ldatm_document_topics_text": (_i32, [_vp, C.c_double, _i32, _vp, C.c_size_t,
                                           C.POINTER(C.c_size_t)]),
@@ -392,6 +395,67 @@ class ParallelTopicModel:
         out = np.zeros(self.numTopics, np.float64)
         _check(self._L.ldatm_get_topic_probabilities(self._h, int(doc), out), "getTopicProbabilities")
         return out
+
+    # ------------------------------- readouts selected on the device
+    def topWords(self, numWords: int):
+        """ldatm_top_words: (word_ids[K, numWords], counts[K, numWords]) int32,
+        count descending, equal counts by ascending word id; -1 / 0 past a
+        topic's last nonzero word.  Only these 2 K numWords numbers leave the
+        device."""
+        n = int(numWords)
+        if not 1 <= n <= capi.TOP_WORDS_MAX:
+            raise ValueError(f"numWords must be in [1, {capi.TOP_WORDS_MAX}]")
+        ids = np.zeros((self.numTopics, n), np.int32)
+        cnt = np.zeros((self.numTopics, n), np.int32)
+        _check(self._L.ldatm_top_words(self._h, n, ids.ctypes.data, cnt.ctypes.data), "topWords")
+        return ids, cnt
+
+    def getTopWords(self, numWords: int) -> list:
+        """Per topic a list of (word, count), at most numWords long, heaviest
+        first: the alphabet's entry, or the word id without an alphabet."""
+        ids, cnt = self.topWords(numWords)
+        name = (lambda w: w) if self.alphabet is None else self.alphabet.lookupObject
+        return [[(name(int(w)), int(c)) for w, c in zip(ids[k], cnt[k]) if w >= 0]
+                for k in range(self.numTopics)]
+
+    def docCounts(self, docs=None) -> np.ndarray:
+        """ldatm_doc_counts: nd[M, K] (int32) of the documents `docs` (global
+        ids, any order; None = all), built on the device from z."""
+        ids, M = _doc_ids(docs, self)
+        nd = np.zeros((M, self.numTopics), np.int32)
+        _check(self._L.ldatm_doc_counts(self._h, M, ids.ctypes.data if ids is not None and M else None,
+                                        nd.ctypes.data), "docCounts")
+        return nd
+
+    def docTopTopics(self, n: int, docs=None):
+        """ldatm_doc_top_topics: (topics[M, n], counts[M, n]) int32 of the
+        documents `docs` (global ids; None = all): the n topics with the largest
+        weight, equal weights by ascending topic; -1 / 0 past K."""
+        n = int(n)
+        if not 1 <= n <= capi.TOP_TOPICS_MAX:
+            raise ValueError(f"n must be in [1, {capi.TOP_TOPICS_MAX}]")
+        ids, M = _doc_ids(docs, self)
+        topics = np.zeros((M, n), np.int32)
+        cnt = np.zeros((M, n), np.int32)
+        _check(self._L.ldatm_doc_top_topics(self._h, n, M, ids.ctypes.data if ids is not None and M else None,
+                                            topics.ctypes.data, cnt.ctypes.data), "docTopTopics")
+        return topics, cnt
+
+    def topTopics(self, docs=None, n: int = 10):
+        """The n heaviest topics of the documents `docs` (global ids; None =
+        all): (topics[M, n] int32, weights[M, n] fp64), weights
+        (alpha_k + n_dk) / (n_d + alphaSum) as printDocumentTopics prints them;
+        past K: topic -1, weight NaN."""
+        topics, cnt = self.docTopTopics(n, docs)
+        ids, M = _doc_ids(docs, self)
+        if len(self.data) == self._shape()[2]:
+            lens = np.array([len(i.data) for i in self.data], np.int64)
+            lens = lens if ids is None else lens[ids]
+        else:       # a loaded model holds no instances here: the rows' sums
+            lens = self.docCounts(docs).sum(axis=1, dtype=np.int64)
+        alpha = self.alpha
+        w = (alpha[np.maximum(topics, 0)] + cnt) / (lens.astype(np.float64) + self.alphaSum)[:, None]
+        return topics, np.where(topics >= 0, w, np.nan)
 
     # ---------------------------------------------------------- outputs
     def _text(self, fn, *args) -> str:
