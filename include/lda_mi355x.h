@@ -498,6 +498,63 @@ lda_status lda_doc_top_topics(lda_ctx* ctx, int32_t m, int64_t doc_begin, int64_
  * context's stream. */
 lda_status lda_doc_counts(lda_ctx* ctx, int64_t doc_begin, int64_t M, const int64_t* docs, int32_t* nd /*[M*K]*/);
 
+/* Topic diagnostics: the integer statistics behind per-topic coherence,
+ * document entropy, rank-1 documents, allocation ratio / count, exclusivity
+ * and the distances from the uniform and corpus distributions, counted on the
+ * device.  The definitions follow Mallet's
+ * TopicModelDiagnostics as this header states them; they are not pinned
+ * against Mallet itself.
+ *
+ * Both calls take K word lists from the caller, word_ids[k*n + i], i < n,
+ * 1 <= n <= LDA_DIAG_WORDS_MAX; a slot holding -1 is empty (anywhere in a
+ * list).  lda_top_words' output is such a list, and so is any other.
+ * Errors of both, all checked on the host before any device work:
+ * LDA_ERR_INVALID_ARG for a NULL ctx, word_ids or output, n out of range, a
+ * word id outside [-1, V), or the same id twice in one topic's list (a word
+ * may stand in several topics' lists); LDA_ERR_STATE with a pending delta.
+ * Device scratch is grow-only and kept by the context: the lists (4 K n
+ * bytes), the lookup table (at most 4 MiB), the results (4 K n (n + 1) / 2 +
+ * 8 K (2 + P) bytes: 34 MiB at K = 4096, n = 64; 28 K n + 8 K bytes for the
+ * word statistics).  Each call waits once for the context's stream and
+ * repeats bit for bit.
+ *
+ * lda_topic_codocuments: counted from THIS shard's documents and current z.
+ * codoc: each topic's packed lower triangle, K * n (n + 1) / 2 int32; cell
+ * (i, j), j <= i, of topic k at codoc[k * n (n + 1) / 2 + i (i + 1) / 2 + j]
+ * = documents holding at least one token of word_ids[k, i] ASSIGNED TO TOPIC
+ * k and at least one of word_ids[k, j] assigned to topic k.  The diagonal is
+ * the word's document frequency under topic k; cells of an empty slot are 0.
+ * doc_stats[k * (2 + P) + c], int64, per topic:
+ *   c = 0: documents with n_dk > 0;
+ *   c = 1: documents whose largest topic count is topic k's (equal counts go
+ *          to the smallest topic id; an empty document counts for no topic);
+ *   c = 2 + i: documents with n_dk > 0 and
+ *          (alpha_k + (double) n_dk) / ((double) n_d + alphaSum) >= props[i],
+ *          lda_doc_top_topics' fp64 expression and alphaSum (alpha added in
+ *          topic order); the division is IEEE, so a weight equal to a
+ *          threshold counts.
+ * 0 <= P <= LDA_DIAG_PROPS_MAX; props strictly ascending in (0, 1], else
+ * LDA_ERR_INVALID_ARG (props may be NULL when P = 0).  A shard of 2^31 or
+ * more documents: LDA_ERR_UNSUPPORTED.  Everything is an integer count, so
+ * the results are exact, independent of any order, and shards' results add.
+ *
+ * lda_topic_word_stats: from the global int32 nw rows and nwsum (the same on
+ * every shard).  counts[k*n + i] = nw[w, k]; totals = sum over k' of
+ * nw[w, k'] (int64); share_sums = sum over k' < K of
+ * (beta + nw[w, k']) / (V beta + nwsum[k']) in fp64, V beta = (double) V *
+ * beta, added in a fixed order: lane l = 0 .. 63 adds k' = l, l + 64, ...
+ * ascending, then the 64 partial sums combine in a butterfly, x[l] += x[l ^ o]
+ * for o = 32, 16, 8, 4, 2, 1.  sumsq[k] = sum over w of nw[w, k]^2 (uint64,
+ * exact: it is at most nwsum[k]^2 < 2^63).  Empty slots give 0. */
+#define LDA_DIAG_WORDS_MAX 64
+#define LDA_DIAG_PROPS_MAX 8
+lda_status lda_topic_codocuments(lda_ctx* ctx, int32_t n, const int32_t* word_ids /*[K*n]*/, int32_t P,
+                                 const double* props /*[P]*/, int32_t* codoc /*[K*n(n+1)/2]*/,
+                                 int64_t* doc_stats /*[K*(2+P)]*/);
+lda_status lda_topic_word_stats(lda_ctx* ctx, int32_t n, const int32_t* word_ids /*[K*n]*/,
+                                int32_t* counts /*[K*n]*/, int64_t* totals /*[K*n]*/,
+                                double* share_sums /*[K*n]*/, uint64_t* sumsq /*[K]*/);
+
 /* Mallet-layout adapter: typeTopicCounts as packed (count << topic_bits) |
  * topic rows sorted descending, rows[row_off[w] .. row_off[w+1]) with
  * row_off[V+1]; row length = min(K, typeTotal[w]) exactly as Mallet allocates
@@ -604,8 +661,9 @@ void lda_debug_fail_host_alloc(int32_t nth);
  * lda_exchange_unpack_lists, lda_counts_checksum; 7 -- lda_set_exchange_cells
  * (four 8-bit cells per packed word); 8 -- lda_score_docs.
  * lda_heldout_loglik and lda_doc_completion, then lda_top_words,
- * lda_doc_top_topics and lda_doc_counts came later and only add symbols, so
- * the version stays 8. */
+ * lda_doc_top_topics and lda_doc_counts, then lda_topic_codocuments and
+ * lda_topic_word_stats came later and only add symbols, so the
+ * version stays 8. */
 #define LDA_ABI_VERSION 8
 const char* lda_version(void);
 int32_t lda_abi_version(void);

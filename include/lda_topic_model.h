@@ -181,6 +181,90 @@ lda_status ldatm_doc_top_topics(ldatm* m, int32_t mtop, int64_t M, const int64_t
                                 int32_t* topics /*[M*mtop]*/, int32_t* counts /*[M*mtop]*/);
 lda_status ldatm_doc_counts(ldatm* m, int64_t M, const int64_t* docs, int32_t* nd /*[M*K]*/);
 
+/* Topic diagnostics: per topic the figures Mallet's
+ * TopicModelDiagnostics reports (train-topics --diagnostics-file), from
+ * integer statistics counted on the device (lda_topic_codocuments,
+ * lda_topic_word_stats, lda_doc_topic_histograms); no copy of z and no V x K
+ * table crosses to the host.  The definitions are written after Mallet's and
+ * are stated here in full; they are not pinned against Mallet itself.
+ *
+ * ldatm_topic_codocuments: lda_topic_codocuments on every shard with the
+ * caller's lists word_ids[K*n] (-1 = empty slot) and thresholds props[P],
+ * summed in int64: codoc[K * n(n+1)/2] (cell (i, j), j <= i, of a topic at
+ * i(i+1)/2 + j) and doc_stats[K * (2 + P)].  Integer sums: the result does not
+ * depend on the number of shards, bit for bit.
+ * Errors (checked before any device work, against the model's K and V):
+ * LDA_ERR_INVALID_ARG for a NULL model, word_ids, props (P > 0) or output, n
+ * outside [1, LDA_DIAG_WORDS_MAX], an id outside [-1, V), the same id twice in
+ * one topic's list, P outside [0, LDA_DIAG_PROPS_MAX], props not strictly
+ * ascending in (0, 1].
+ *
+ * ldatm_topic_statistics: ldatm_top_words(n) and lda_topic_word_stats on
+ * shard 0 (word_ids, counts, totals, share_sums [K*n], sumsq [K], all
+ * outputs), then ldatm_topic_codocuments with those lists and Mallet's
+ * LDATM_DIAG_PROPS = 7 proportions {0.01, 0.02, 0.05, 0.1, 0.2, 0.3, 0.5}
+ * (doc_stats [K * 9]).
+ *
+ * ldatm_diagnostics_finish: host only, no model and no device.  From K, V, n,
+ * beta, nwsum[K], the summed topicDocCounts topic_doc_counts[K*(max_len+1)]
+ * (row k, cell c: documents in which topic k has count c; lda_doc_topic_
+ * histograms) and the statistics above it writes out[K * LDATM_DIAG_COLUMNS],
+ * column c of topic k at out[k * LDATM_DIAG_COLUMNS + c].  With T = nwsum[k],
+ * N = sum of nwsum, D_k = doc_stats[k][0], the topic's m non-empty slots in
+ * list order (c_i, t_i, s_i their counts, totals, share_sums; C its triangle,
+ * H its histogram row), natural logarithms, a ratio with a zero denominator
+ * and a term x log(..) with x = 0 both 0, and every column 0 when T = 0:
+ *   TOKENS            T
+ *   DOCUMENT_ENTROPY  log T - (sum_{c=1..max_len} H[c] (c log c)) / T,
+ *                     added in ascending c
+ *   COHERENCE         sum_{i=1..m-1} sum_{j=0..i-1}
+ *                     log((C[i,j] + beta) / (C[j,j] + beta)), i outer
+ *   UNIFORM_DIST      sum_i p_i log(p_i V), p_i = c_i / T
+ *   CORPUS_DIST       sum_i p_i log(p_i / (t_i / N))
+ *   EFF_NUM_WORDS     T T / sumsq[k]
+ *   TOKEN_DOC_DIFF    sum_i (p_i log(p_i / mu_i) + q_i log(q_i / mu_i)) / 2,
+ *                     here p_i = c_i / sum_j c_j, q_i = C[i,i] / sum_j C[j,j],
+ *                     mu_i = (p_i + q_i) / 2
+ *   RANK_1_DOCS       doc_stats[k][1] / D_k
+ *   ALLOCATION_RATIO  documents at 0.5 / documents at 0.02
+ *   ALLOCATION_COUNT  documents at 0.3 / D_k
+ *   EXCLUSIVITY       (1 / m) sum_i ((beta + c_i) / (V beta + T)) / s_i
+ * LDA_ERR_INTERNAL when a topic's histogram row does not add up to D_k (the
+ * two are counted by different kernels); LDA_ERR_INVALID_ARG for a NULL
+ * argument or n outside [1, LDA_DIAG_WORDS_MAX].
+ *
+ * ldatm_topic_diagnostics: ldatm_topic_statistics, nwsum, the shards'
+ * histograms of the current z and ldatm_diagnostics_finish; out
+ * [K * LDATM_DIAG_COLUMNS], and the lists used in word_ids[K*n] unless NULL.
+ * Errors: LDA_ERR_INVALID_ARG for a NULL model or out, or n out of range
+ * (before any device work). */
+#define LDATM_DIAG_PROPS 7
+#define LDATM_DIAG_COLUMNS 11
+#define LDATM_DIAG_TOKENS 0
+#define LDATM_DIAG_DOCUMENT_ENTROPY 1
+#define LDATM_DIAG_COHERENCE 2
+#define LDATM_DIAG_UNIFORM_DIST 3
+#define LDATM_DIAG_CORPUS_DIST 4
+#define LDATM_DIAG_EFF_NUM_WORDS 5
+#define LDATM_DIAG_TOKEN_DOC_DIFF 6
+#define LDATM_DIAG_RANK_1_DOCS 7
+#define LDATM_DIAG_ALLOCATION_RATIO 8
+#define LDATM_DIAG_ALLOCATION_COUNT 9
+#define LDATM_DIAG_EXCLUSIVITY 10
+lda_status ldatm_topic_codocuments(ldatm* m, int32_t n, const int32_t* word_ids /*[K*n]*/, int32_t P,
+                                   const double* props /*[P]*/, int64_t* codoc /*[K*n(n+1)/2]*/,
+                                   int64_t* doc_stats /*[K*(2+P)]*/);
+lda_status ldatm_topic_statistics(ldatm* m, int32_t n, int32_t* word_ids /*[K*n]*/, int32_t* counts /*[K*n]*/,
+                                  int64_t* totals /*[K*n]*/, double* share_sums /*[K*n]*/, uint64_t* sumsq /*[K]*/,
+                                  int64_t* codoc /*[K*n(n+1)/2]*/, int64_t* doc_stats /*[K*9]*/);
+lda_status ldatm_diagnostics_finish(int32_t K, int32_t V, int32_t n, double beta, const int32_t* nwsum /*[K]*/,
+                                    int32_t max_len, const int64_t* topic_doc_counts /*[K*(max_len+1)]*/,
+                                    const int32_t* word_ids, const int32_t* counts, const int64_t* totals,
+                                    const double* share_sums, const uint64_t* sumsq, const int64_t* codoc,
+                                    const int64_t* doc_stats, double* out /*[K*LDATM_DIAG_COLUMNS]*/);
+lda_status ldatm_topic_diagnostics(ldatm* m, int32_t n, double* out /*[K*LDATM_DIAG_COLUMNS]*/,
+                                   int32_t* word_ids /*[K*n] or NULL*/);
+
 /* printDocumentTopics(File) (threshold 0, max -1 = all) and its text:
  * "#doc source topic proportion ...", then per document
  * "<doc> <source|null-source> <topic> <weight> ... \n" (weights descending,

@@ -34,6 +34,9 @@ SCORE_METRICS = {"cosine": 0, "mse": 1}
 # LDA_TOP_WORDS_MAX / LDA_TOP_TOPICS_MAX of lda_mi355x.h
 TOP_WORDS_MAX = 64
 TOP_TOPICS_MAX = 64
+# LDA_DIAG_WORDS_MAX / LDA_DIAG_PROPS_MAX of lda_mi355x.h
+DIAG_WORDS_MAX = 64
+DIAG_PROPS_MAX = 8
 
 
 def score_metric(metric) -> int:
@@ -142,6 +145,8 @@ SIGNATURES = {
     "lda_top_words": (C.c_int32, [_vp, C.c_int32, _vp, _vp]),
     "lda_doc_top_topics": (C.c_int32, [_vp, C.c_int32, C.c_int64, C.c_int64, _vp, _vp, _vp]),
     "lda_doc_counts": (C.c_int32, [_vp, C.c_int64, C.c_int64, _vp, _vp]),
+    "lda_topic_codocuments": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
+    "lda_topic_word_stats": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "lda_to_mallet_packed": (C.c_int32, [_vp, _vp, _i64p, C.POINTER(C.c_int32)]),
     "lda_max_doc_length": (C.c_int32, [_vp, C.POINTER(C.c_int32)]),
     "lda_doc_topic_histograms": (C.c_int32, [_vp, C.c_int32, _i32p, _i32p]),

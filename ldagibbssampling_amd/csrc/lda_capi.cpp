@@ -234,6 +234,13 @@ constexpr int64_t TOP_WORDS_WAVES = 1024;
 // document) and documents per chunk
 constexpr int64_t READOUT_CELLS = int64_t(1) << 23;
 constexpr int64_t READOUT_DOCS = int64_t(1) << 20;
+// lda_topic_codocuments: the co-document kernel's waves per block (they share
+// the block's triangles; 16 waves x 2 blocks of 64 KiB keep 32 waves on a CU,
+// 2.3x faster than 4 waves x 4 blocks at V = 1e5, K = 512: DESIGN 9e) and its
+// blocks (document slabs x topic groups) per CU; every slab adds its nonzero
+// cells to the result once
+constexpr int CODOC_WAVES = 16;
+constexpr int64_t CODOC_BLOCKS_PER_CU = 2;
 
 }  // namespace
 
@@ -320,6 +327,14 @@ struct lda_ctx {
   int32_t* ro_out = nullptr;
   int64_t* ro_docs = nullptr;
   size_t ro_cap[3] = {};
+  // lda_topic_codocuments / lda_topic_word_stats: grow-only scratch -- the
+  // word lists [K n], the (word, topic) -> slot table, the integer results
+  // and lda_topic_word_stats' fp64 sums
+  int32_t* dg_ids = nullptr;
+  unsigned long long* dg_table = nullptr;
+  unsigned long long* dg_out = nullptr;
+  double* dg_shares = nullptr;
+  size_t dg_cap[4] = {};
   // 16-bit rows of the snapshot (LDA_SAMPLER_DENSE)
   uint16_t* nw16 = nullptr;
   uint8_t* wide = nullptr;
@@ -468,6 +483,7 @@ struct lda_ctx {
                     (void*)score_theta, (void*)score_out, (void*)score_docs,
                     (void*)held_theta, (void*)held_ll, (void*)held_inv, (void*)held_words, (void*)held_off,
                     (void*)ro_lists, (void*)ro_out, (void*)ro_docs,
+                    (void*)dg_ids, (void*)dg_table, (void*)dg_out, (void*)dg_shares,
                     (void*)perm, (void*)items, (void*)warm.range_doc, (void*)steady.range_doc,
                     (void*)big.tab, (void*)big.tab_m1, (void*)big.F, (void*)big.pfx, (void*)big.scal})
       if (p) (void)hipFree(p);
@@ -2426,17 +2442,20 @@ lda_status lda_score_docs(lda_ctx* c, int32_t metric, int64_t Q, const double* t
 
 namespace {
 
-// grow-only readout scratch (lda_ctx::ro_*; capacities in bytes)
-hipError_t ro_need_bytes(lda_ctx* c, void** ptr, size_t bytes, int slot) {
-  if (bytes <= c->ro_cap[slot]) return hipSuccess;
+// grow-only readout scratch (lda_ctx::ro_* / dg_*; capacities in bytes)
+hipError_t grow_bytes(void** ptr, size_t* cap, size_t bytes) {
+  if (bytes <= *cap) return hipSuccess;
   if (*ptr) (void)hipFree(*ptr);
   *ptr = nullptr;
-  c->ro_cap[slot] = 0;
+  *cap = 0;
   const hipError_t e = hipMalloc(ptr, bytes);
-  if (e == hipSuccess) c->ro_cap[slot] = bytes;
+  if (e == hipSuccess) *cap = bytes;
   return e;
 }
-#define ro_need(c, ptr, n, slot) ro_need_bytes((c), reinterpret_cast<void**>(&(ptr)), (n) * sizeof(*(ptr)), (slot))
+#define ro_need(c, ptr, n, slot) \
+  grow_bytes(reinterpret_cast<void**>(&(ptr)), &(c)->ro_cap[(slot)], (n) * sizeof(*(ptr)))
+#define dg_need(c, ptr, n, slot) \
+  grow_bytes(reinterpret_cast<void**>(&(ptr)), &(c)->dg_cap[(slot)], (n) * sizeof(*(ptr)))
 
 // the document arguments lda_score_docs takes, checked the same way
 lda_status check_doc_list(const lda_ctx* c, int64_t doc_begin, int64_t M, const int64_t* docs) {
@@ -2560,6 +2579,151 @@ lda_status lda_doc_top_topics(lda_ctx* c, int32_t m, int64_t doc_begin, int64_t 
   if (M == 0) return LDA_OK;
   if (!topics || !counts) return fail(LDA_ERR_INVALID_ARG, "null output");
   return doc_readout(c, m, doc_begin, M, docs, topics, counts);
+  });
+}
+
+namespace {
+
+// the K word lists of lda_topic_codocuments / lda_topic_word_stats
+lda_status check_word_lists(const lda_ctx* c, int32_t n, const int32_t* word_ids) {
+  if (n < 1 || n > LDA_DIAG_WORDS_MAX) return fail(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_DIAG_WORDS_MAX]");
+  if (!word_ids) return fail(LDA_ERR_INVALID_ARG, "null word_ids");
+  for (int k = 0; k < c->K; ++k) {
+    const int32_t* l = word_ids + (size_t)k * n;
+    for (int i = 0; i < n; ++i) {
+      if (l[i] < -1 || l[i] >= c->V) return fail(LDA_ERR_INVALID_ARG, "word_ids: id outside [-1, V)");
+      for (int j = 0; l[i] >= 0 && j < i; ++j)
+        if (l[j] == l[i]) return fail(LDA_ERR_INVALID_ARG, "word_ids: the same id twice in one topic's list");
+    }
+  }
+  return LDA_OK;
+}
+
+}  // namespace
+
+lda_status lda_topic_codocuments(lda_ctx* c, int32_t n, const int32_t* word_ids, int32_t P, const double* props,
+                                 int32_t* codoc, int64_t* doc_stats) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (lda_status s = check_word_lists(c, n, word_ids); s != LDA_OK) return s;
+  if (P < 0 || P > LDA_DIAG_PROPS_MAX) return fail(LDA_ERR_INVALID_ARG, "P must be in [0, LDA_DIAG_PROPS_MAX]");
+  if (P > 0 && !props) return fail(LDA_ERR_INVALID_ARG, "null props");
+  for (int i = 0; i < P; ++i)
+    if (!(props[i] > 0.0 && props[i] <= 1.0) || (i > 0 && !(props[i] > props[i - 1])))
+      return fail(LDA_ERR_INVALID_ARG, "props must be strictly ascending in (0, 1]");
+  if (!codoc || !doc_stats) return fail(LDA_ERR_INVALID_ARG, "null output");
+  if (c->pending) return fail(LDA_ERR_STATE, "codocuments with a pending delta: call lda_apply first");
+  if (c->D >= (int64_t(1) << 31)) return fail(LDA_ERR_UNSUPPORTED, "codocuments: 2^31 or more documents in a shard");
+  const int32_t K = c->K;
+  const size_t cells = (size_t)K * (size_t)n, tri = (size_t)n * (n + 1) / 2;
+  const size_t stat_cells = (size_t)K * (size_t)(2 + P);
+  // the (word, topic) -> slot table: a power of two at least twice the entries
+  size_t entries = 0;
+  for (size_t i = 0; i < cells; ++i) entries += word_ids[i] >= 0;
+  size_t slots = 64;
+  while (slots < 2 * entries) slots <<= 1;
+  std::vector<unsigned long long> table = host_vector<unsigned long long>(slots);
+  for (int k = 0; k < K; ++k)
+    for (int i = 0; i < n; ++i) {
+      const int32_t w = word_ids[(size_t)k * n + i];
+      if (w < 0) continue;
+      const uint64_t key = (uint64_t)w * (uint64_t)c->Kp + (uint64_t)k;
+      size_t h = (size_t)lda::codoc_hash(key) & (slots - 1);
+      while (table[h]) h = (h + 1) & (slots - 1);
+      table[h] = ((key + 1) << 6) | (unsigned long long)i;
+    }
+  double A = 0.0;
+  for (int k = 0; k < K; ++k) A += c->alpha[(size_t)k];
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(dg_need(c, c->dg_table, slots, 1));
+  // the triangles (int32) then the document statistics (8-byte aligned)
+  const size_t tri_words = (K * tri + 1) / 2;
+  HIP_TRY(dg_need(c, c->dg_out, tri_words + stat_cells, 2));
+  int32_t* d_codoc = reinterpret_cast<int32_t*>(c->dg_out);
+  unsigned long long* d_stats = c->dg_out + tri_words;
+  HIP_TRY(hipMemcpyAsync(c->dg_table, table.data(), sizeof(unsigned long long) * slots, hipMemcpyHostToDevice,
+                         c->stream));
+  HIP_TRY(hipMemsetAsync(c->dg_out, 0, sizeof(unsigned long long) * (tri_words + stat_cells), c->stream));
+  lda::CodocArgs a{};
+  a.words = c->words;
+  a.z = c->z;
+  a.doc_off = c->doc_off;
+  a.D = c->D;
+  a.table = c->dg_table;
+  a.table_mask = (uint32_t)(slots - 1);
+  a.K = K;
+  a.Kp = c->Kp;
+  a.n = n;
+  a.group_topics = lda::codoc_group_topics(K, n, CODOC_WAVES);
+  a.codoc = d_codoc;
+  const int64_t groups = (K + a.group_topics - 1) / a.group_topics;
+  const int64_t doc_blocks = std::max<int64_t>(1, (c->D + 3) / 4);
+  const int slabs = (int)std::min<int64_t>(std::max<int64_t>(1, (c->D + CODOC_WAVES - 1) / CODOC_WAVES),
+                                           std::max<int64_t>(1, CODOC_BLOCKS_PER_CU * c->cus / groups));
+  HIP_TRY(lda::launch_codoc(a, slabs, CODOC_WAVES, c->stream));
+  lda::DocDiagArgs s{};
+  s.z = c->z;
+  s.doc_off = c->doc_off;
+  s.D = c->D;
+  s.alpha = c->alpha_d;
+  s.A = A;
+  for (int i = 0; i < P; ++i) s.props[i] = props[i];
+  s.K = K;
+  s.Kp = c->Kp;
+  s.P = P;
+  s.stats = d_stats;
+  HIP_TRY(lda::launch_doc_diag(s, (int)std::min<int64_t>(doc_blocks, (int64_t)c->cus * 8), c->stream));
+  HIP_TRY(hipMemcpyAsync(codoc, d_codoc, sizeof(int32_t) * K * tri, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(doc_stats, d_stats, sizeof(int64_t) * stat_cells, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LDA_OK;
+  });
+}
+
+lda_status lda_topic_word_stats(lda_ctx* c, int32_t n, const int32_t* word_ids, int32_t* counts, int64_t* totals,
+                                double* share_sums, uint64_t* sumsq) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (lda_status s = check_word_lists(c, n, word_ids); s != LDA_OK) return s;
+  if (!counts || !totals || !share_sums || !sumsq) return fail(LDA_ERR_INVALID_ARG, "null output");
+  if (c->pending) return fail(LDA_ERR_STATE, "word statistics with a pending delta: call lda_apply first");
+  const int32_t K = c->K;
+  const size_t cells = (size_t)K * (size_t)n;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(dg_need(c, c->dg_ids, cells, 0));
+  // totals [K n], sumsq [K] (8 bytes each), then counts [K n] (int32)
+  HIP_TRY(dg_need(c, c->dg_out, cells + (size_t)K + (cells + 1) / 2, 2));
+  HIP_TRY(dg_need(c, c->dg_shares, cells, 3));
+  HIP_TRY(hipMemcpyAsync(c->dg_ids, word_ids, sizeof(int32_t) * cells, hipMemcpyHostToDevice, c->stream));
+  lda::WordStatsArgs a{};
+  a.nw = c->nw;
+  a.nwsum = c->nwsum;
+  a.ids = c->dg_ids;
+  a.V = c->V;
+  a.K = K;
+  a.Kp = c->Kp;
+  a.n = n;
+  a.beta = c->beta;
+  a.vbeta = (double)c->V * c->beta;
+  // k_sumsq's slabs as lda_top_words cuts the rows
+  const int64_t G = c->Kp / 64;
+  int64_t slabs = std::max<int64_t>(1, std::min<int64_t>((c->V + TOP_WORDS_SLAB_ROWS - 1) / TOP_WORDS_SLAB_ROWS,
+                                                         std::max<int64_t>(1, TOP_WORDS_WAVES / G)));
+  const int64_t slab_rows = std::max<int64_t>(1, (c->V + slabs - 1) / slabs);
+  a.slabs = (int32_t)std::max<int64_t>(1, (c->V + slab_rows - 1) / slab_rows);
+  a.slab_rows = (int32_t)slab_rows;
+  a.totals = reinterpret_cast<long long*>(c->dg_out);
+  a.sumsq = c->dg_out + cells;
+  a.counts = reinterpret_cast<int32_t*>(c->dg_out + cells + K);
+  a.share_sums = c->dg_shares;
+  HIP_TRY(hipMemsetAsync(a.sumsq, 0, sizeof(unsigned long long) * (size_t)K, c->stream));
+  HIP_TRY(lda::launch_word_stats(a, c->stream));
+  HIP_TRY(hipMemcpyAsync(counts, a.counts, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(totals, a.totals, sizeof(int64_t) * cells, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(share_sums, a.share_sums, sizeof(double) * cells, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(sumsq, a.sumsq, sizeof(uint64_t) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LDA_OK;
   });
 }
 

@@ -268,6 +268,69 @@ struct DocReadoutArgs {
 };
 hipError_t launch_doc_counts(const DocReadoutArgs& a, int blocks, hipStream_t st);
 hipError_t launch_doc_top_topics(const DocReadoutArgs& a, int blocks, hipStream_t st);
+// lda_topic_codocuments, the co-document count (k_codoc): grid (document
+// slabs, topic groups); a block keeps the packed triangles of its
+// group_topics topics in LDS, a wave takes a document, marks the listed words
+// it holds under each topic of the group in a 64-bit mask per topic and adds
+// the masks' pairs into the triangles; the block adds its nonzero cells to
+// codoc (zeroed by the caller) once at the end.  (word, topic) -> slot goes
+// through an open-addressing table keyed w * Kp + k: entry
+// ((key + 1) << 6) | slot, 0 = empty, linear probing from
+// codoc_hash(key) & table_mask; at most half full, so a probe ends.
+constexpr int DIAG_WORDS_MAX = 64;
+constexpr int DIAG_PROPS_MAX = 8;
+constexpr size_t CODOC_LDS_BYTES = 64 * 1024;
+// topics per group of a block of `waves` waves: a mask per wave (8 bytes
+// each) and a triangle per topic
+constexpr int codoc_group_topics(int K, int n, int waves) {
+  const int per = 8 * waves + 4 * (n * (n + 1) / 2), g = (int)(CODOC_LDS_BYTES / per);
+  return g < K ? g : K;
+}
+constexpr uint64_t codoc_hash(uint64_t key) { return (key * 0x9E3779B97F4A7C15ull) >> 32; }
+struct CodocArgs {
+  const int32_t* words;
+  const int32_t* z;
+  const int64_t* doc_off;
+  int64_t D;
+  const unsigned long long* table;   // [table_mask + 1]
+  uint32_t table_mask;
+  int32_t K, Kp, n, group_topics;
+  int32_t* codoc;                    // [K * n (n + 1) / 2], zeroed
+};
+hipError_t launch_codoc(const CodocArgs& a, int slabs, int waves, hipStream_t st);
+// lda_topic_codocuments' document statistics (k_doc_diag): one wave per
+// document, the counts in the per-wave LDS histogram, read back through the
+// document's own tokens.  stats[k * (2 + P) + c] (zeroed by the caller); the
+// increments go through per-block LDS counters when lds_counters is set (the
+// launcher sets it when 16 Kp + 4 K (2 + P) bytes fit 64 KiB), else straight
+// to stats.
+struct DocDiagArgs {
+  const int32_t* z;
+  const int64_t* doc_off;
+  int64_t D;
+  const double* alpha;      // [K]
+  double A;                 // alpha[0] + ... + alpha[K-1], added in that order
+  double props[DIAG_PROPS_MAX];   // ascending; props[i >= P] unused
+  int32_t K, Kp, P, lds_counters;
+  unsigned long long* stats;
+};
+hipError_t launch_doc_diag(DocDiagArgs a, int blocks, hipStream_t st);
+// lda_topic_word_stats: k_word_stats, one wave per listed word (cell of
+// ids[K * n]); k_sumsq, the column sums of nw squared (sumsq zeroed by the
+// caller, slabs x Kp / 64 one-wave blocks adding one integer per column).
+struct WordStatsArgs {
+  const int32_t* nw;        // [V * Kp]
+  const int32_t* nwsum;     // [Kp]
+  const int32_t* ids;       // [K * n], -1 = empty
+  int32_t V, K, Kp, n;
+  double beta, vbeta;
+  int32_t slabs, slab_rows;
+  int32_t* counts;                 // [K * n]
+  long long* totals;               // [K * n]
+  double* share_sums;              // [K * n]
+  unsigned long long* sumsq;       // [K], zeroed
+};
+hipError_t launch_word_stats(const WordStatsArgs& a, hipStream_t st);
 // lda_heldout_loglik (k_doc_completion): the scored tokens of Dh held-out
 // documents against the int32 nw rows.  A wave takes a document's tokens in
 // batches of doc_completion_batch(C): 64 up to C = 8, 16 above (the batch's

@@ -3386,6 +3386,187 @@ __global__ __launch_bounds__(256) void k_doc_top_topics(const DocReadoutArgs a) 
   }
 }
 
+// lda_topic_codocuments: codoc[k][i, j] = documents holding a token of word
+// ids[k, i] and a token of ids[k, j], both assigned to topic k.  Block
+// (slab s, group g) of W waves (the launcher's choice, up to 16) owns topics
+// [g Gt, (g + 1) Gt) and documents W s + wave, stepping by W gridDim.x; its
+// LDS holds a presence mask per (wave, topic) and the group's packed
+// triangles.  A wave walks its
+// document's tokens: a token whose topic is outside the group costs its z
+// alone; one inside looks (word, topic) up in the hash table and sets the
+// slot's bit in the topic's mask (an LDS or; a document's repeats fold here).
+// Then lane t takes topic t's mask, clears it and adds 1 to cell
+// i (i + 1) / 2 + j for every pair of set bits j <= i (LDS adds: the block's
+// waves share the triangles).  At the end the block adds its nonzero cells
+// to the output: one integer atomic per nonzero cell per block, consecutive
+// lanes on consecutive cells.  Integers only, so the result does not depend
+// on the grid or the order.
+__global__ __launch_bounds__(1024) void k_codoc(const CodocArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long cd_lds[];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, threads = blockDim.x, waves = threads >> 6;
+  const int Gt = a.group_topics, T = a.n * (a.n + 1) / 2;
+  const int k0 = (int)blockIdx.y * Gt, gt = min(Gt, a.K - k0);
+  unsigned long long* mask = cd_lds + wid * Gt;
+  int32_t* tri = reinterpret_cast<int32_t*>(cd_lds + waves * Gt);
+  for (int i = threadIdx.x; i < gt * T; i += threads) tri[i] = 0;
+  for (int i = lane; i < gt; i += 64) mask[i] = 0;
+  __syncthreads();
+  const int32_t* __restrict__ z = a.z;
+  const int32_t* __restrict__ words = a.words;
+  const unsigned long long* __restrict__ table = a.table;
+  for (int64_t d = (int64_t)blockIdx.x * waves + wid; d < a.D; d += (int64_t)gridDim.x * waves) {
+    const int64_t t1 = a.doc_off[d + 1];
+    for (int64_t i = a.doc_off[d] + lane; i < t1; i += 64) {
+      const uint32_t kl = (uint32_t)(z[i] - k0);
+      if (kl >= (uint32_t)gt) continue;
+      const uint64_t key = (uint64_t)(uint32_t)words[i] * (uint32_t)a.Kp + (kl + (uint32_t)k0);
+      for (uint32_t h = (uint32_t)codoc_hash(key) & a.table_mask;; h = (h + 1) & a.table_mask) {
+        const unsigned long long e = table[h];
+        if (e == 0) break;
+        if ((e >> 6) == key + 1) {
+          atomicOr(&mask[kl], 1ull << (e & 63));
+          break;
+        }
+      }
+    }
+    wave_lds_fence();
+    for (int t = lane; t < gt; t += 64) {
+      const unsigned long long m = mask[t];
+      if (m == 0) continue;
+      mask[t] = 0;
+      int32_t* cell = tri + t * T;
+      for (unsigned long long mi = m; mi; mi &= mi - 1) {
+        const int i = __builtin_ctzll(mi);
+        int32_t* row = cell + i * (i + 1) / 2;
+        for (unsigned long long mj = m & ((2ull << i) - 1); mj; mj &= mj - 1) atomicAdd(&row[__builtin_ctzll(mj)], 1);
+      }
+    }
+    wave_lds_fence();
+  }
+  __syncthreads();
+  int32_t* __restrict__ out = a.codoc + (size_t)k0 * T;
+  for (int i = threadIdx.x; i < gt * T; i += threads) {
+    const int32_t v = tri[i];
+    if (v) atomicAdd(&out[i], v);
+  }
+}
+
+// lda_topic_codocuments' document statistics.  One wave per document; the
+// topic counts go into the per-wave LDS histogram and come back through the
+// document's own tokens (the first lane to take topic k, an LDS exchange with
+// 0, holds its count c and leaves the cell clear), so a document costs O(its
+// tokens).  Per nonzero topic: [0] += 1 and [2 + i] += 1 for every threshold
+// the fp64 weight (alpha_k + c) / (n_d + A) reaches -- lda_doc_top_topics'
+// expression; the thresholds ascend, so they are the first t of them.  [1]:
+// the wave-wide maximum of c << 32 | (0xFFFFFFFF - k), the largest count and
+// of equal counts the smallest topic; an empty document has none.  LDS is
+// [4][Kp] histograms and, with lds_counters, [K (2 + P)] int32 block counters
+// flushed once (a block sees fewer than 2^31 documents).
+__global__ __launch_bounds__(256) void k_doc_diag(const DocDiagArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int32_t h[];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int C = 2 + a.P, cells = a.K * C;
+  int32_t* hist = h + wid * a.Kp;
+  int32_t* blk = h + 4 * a.Kp;
+  const bool lds = a.lds_counters != 0;
+  for (int i = lane; i < a.Kp; i += 64) hist[i] = 0;
+  if (lds)
+    for (int i = threadIdx.x; i < cells; i += 256) blk[i] = 0;
+  __syncthreads();
+  const int32_t* __restrict__ z = a.z;
+  const double* __restrict__ alpha = a.alpha;
+  unsigned long long* __restrict__ stats = a.stats;
+  auto bump = [&](int idx) {
+    if (lds)
+      atomicAdd(&blk[idx], 1);
+    else
+      atomicAdd(&stats[idx], 1ull);
+  };
+  for (int64_t d = (int64_t)blockIdx.x * 4 + wid; d < a.D; d += (int64_t)gridDim.x * 4) {
+    const int64_t t0 = a.doc_off[d], t1 = a.doc_off[d + 1];
+    for (int64_t i = t0 + lane; i < t1; i += 64) atomicAdd(&hist[z[i]], 1);
+    wave_lds_fence();
+    const double S = (double)(t1 - t0) + a.A;
+    unsigned long long best = 0;
+    for (int64_t i = t0 + lane; i < t1; i += 64) {
+      const int k = z[i];
+      const int32_t c = atomicExch(&hist[k], 0);
+      if (c <= 0) continue;
+      const unsigned long long key = ((unsigned long long)(uint32_t)c << 32) | (0xFFFFFFFFu - (uint32_t)k);
+      best = key > best ? key : best;
+      const double w = (alpha[k] + (double)c) / S;
+      bump(k * C);
+#pragma unroll
+      for (int u = 0; u < DIAG_PROPS_MAX; ++u)
+        if (u < a.P && w >= a.props[u]) bump(k * C + 2 + u);
+    }
+    best = wave_max_u64(best);
+    if (lane == 0 && best != 0) bump((int)(0xFFFFFFFFu - (uint32_t)best) * C + 1);
+    wave_lds_fence();
+  }
+  if (!lds) return;
+  __syncthreads();
+  for (int i = threadIdx.x; i < cells; i += 256) {
+    const int32_t v = blk[i];
+    if (v) atomicAdd(&stats[i], (unsigned long long)v);
+  }
+}
+
+// lda_topic_word_stats: one wave per cell of the lists.  counts = nw[w, k];
+// totals = the row's integer sum; share_sums = sum over k' < K of
+// (beta + nw[w, k']) / (V beta + nwsum[k']) in fp64: lane l adds
+// k' = l, l + 64, ... in ascending order, then the lanes combine in the xor
+// butterfly 32, 16, 8, 4, 2, 1 (wave_sum_d): a fixed order, every lane the
+// same bits.
+__global__ __launch_bounds__(64) void k_word_stats(const WordStatsArgs a) {
+  const int lane = threadIdx.x, cell = blockIdx.x, k = cell / a.n;
+  const int32_t w = a.ids[cell];
+  if (w < 0) {
+    if (lane == 0) {
+      a.counts[cell] = 0;
+      a.totals[cell] = 0;
+      a.share_sums[cell] = 0.0;
+    }
+    return;
+  }
+  const int32_t* __restrict__ row = a.nw + (size_t)w * a.Kp;
+  const int32_t* __restrict__ nwsum = a.nwsum;
+  long long tot = 0;
+  double s = 0.0;
+  for (int kk = lane; kk < a.K; kk += 64) {
+    const int32_t c = row[kk];
+    tot += c;
+    s += (a.beta + (double)c) / (a.vbeta + (double)nwsum[kk]);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
+  s = wave_sum_d(s);
+  if (lane == 0) {
+    a.counts[cell] = row[k];
+    a.totals[cell] = tot;
+    a.share_sums[cell] = s;
+  }
+}
+
+// lda_topic_word_stats' sumsq[k] = sum over w of nw[w, k]^2: one wave per
+// (slab of rows, group of 64 topics) as k_top_words_slab cuts them, lane l on
+// column group * 64 + l, eight rows in flight; one integer atomic per column
+// per slab.
+__global__ __launch_bounds__(64) void k_sumsq(const WordStatsArgs a) {
+  const int lane = threadIdx.x, s = blockIdx.x, k = (int)blockIdx.y * 64 + lane;
+  const int32_t* __restrict__ col = a.nw + k;
+  const int64_t w0 = (int64_t)s * a.slab_rows, w1 = min((int64_t)a.V, w0 + a.slab_rows);
+  unsigned long long acc = 0;
+  for (int64_t w = w0; w < w1; w += 8) {
+    int32_t c[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) c[u] = w + u < w1 ? col[(size_t)(w + u) * a.Kp] : 0;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc += (unsigned long long)((long long)c[u] * c[u]);
+  }
+  if (k < a.K && acc) atomicAdd(&a.sumsq[k], acc);
+}
+
 // lda_heldout_loglik: inv[k] = 1 / (nwsum[k] + V beta) in fp64, 0 for the
 // padded topics.
 __global__ __launch_bounds__(256) void k_heldout_inv(const int32_t* __restrict__ nwsum, double vbeta, int32_t K,
@@ -4225,6 +4406,40 @@ hipError_t launch_doc_top_topics(const DocReadoutArgs& a, int blocks, hipStream_
   if (a.M <= 0) return hipSuccess;
   if (a.m < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_doc_top_topics, dim3(blocks), dim3(256), 4 * (size_t)a.Kp * sizeof(int32_t), st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_codoc(const CodocArgs& a, int slabs, int waves, hipStream_t st) {
+  if (a.n < 1 || a.n > DIAG_WORDS_MAX || a.K < 1 || slabs < 1 || waves < 1 || waves > 16 || a.group_topics < 1 ||
+      a.group_topics != codoc_group_topics(a.K, a.n, waves) || (a.table_mask & (a.table_mask + 1)) != 0)
+    return hipErrorInvalidValue;
+  if (a.D <= 0) return hipSuccess;
+  const int Gt = a.group_topics, groups = (a.K + Gt - 1) / Gt;
+  // masks [waves][Gt] and triangles [Gt][n (n + 1) / 2]: at most CODOC_LDS_BYTES
+  const size_t lds = (size_t)Gt * (8 * (size_t)waves + 4 * (size_t)(a.n * (a.n + 1) / 2));
+  hipLaunchKernelGGL(k_codoc, dim3(slabs, groups), dim3(64 * waves), lds, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_doc_diag(DocDiagArgs a, int blocks, hipStream_t st) {
+  if (a.P < 0 || a.P > DIAG_PROPS_MAX || blocks < 1) return hipErrorInvalidValue;
+  if (a.D <= 0) return hipSuccess;
+  // 64 KiB at Kp = 4096 for the histograms alone: the counters go to global there
+  size_t lds = 4 * (size_t)a.Kp * sizeof(int32_t);
+  const size_t counters = (size_t)a.K * (2 + a.P) * sizeof(int32_t);
+  a.lds_counters = lds + counters <= 64 * 1024;
+  if (a.lds_counters) lds += counters;
+  hipLaunchKernelGGL(k_doc_diag, dim3(blocks), dim3(256), lds, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_word_stats(const WordStatsArgs& a, hipStream_t st) {
+  if (a.n < 1 || a.n > DIAG_WORDS_MAX || a.K < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_word_stats, dim3(a.K * a.n), dim3(64), 0, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || a.V < 1) return e;
+  if (a.slabs < 1 || (int64_t)a.slabs * a.slab_rows < a.V) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_sumsq, dim3(a.slabs, a.Kp / 64), dim3(64), 0, st, a);
   return hipGetLastError();
 }
 

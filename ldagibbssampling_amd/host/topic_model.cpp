@@ -27,6 +27,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -1014,6 +1015,151 @@ void ParallelTopicModel::docTopTopics(int32_t mtop, int64_t M, const int64_t* do
 
 void ParallelTopicModel::docCounts(int64_t M, const int64_t* docs, int32_t* nd) { docReadout(0, M, docs, nd, nullptr); }
 
+namespace {
+// Mallet's TopicModelDiagnostics thresholds (its DEFAULT_DOC_PROPORTIONS)
+constexpr double DIAG_PROPS[LDATM_DIAG_PROPS] = {0.01, 0.02, 0.05, 0.1, 0.2, 0.3, 0.5};
+}  // namespace
+
+void ParallelTopicModel::topicCodocuments(int32_t n, const int32_t* word_ids, int32_t P, const double* props,
+                                          int64_t* codoc, int64_t* doc_stats) {
+  // lda_topic_codocuments' checks, against the model's K and V, before any device work
+  if (n < 1 || n > LDA_DIAG_WORDS_MAX) raise(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_DIAG_WORDS_MAX]");
+  if (!word_ids) raise(LDA_ERR_INVALID_ARG, "null word_ids");
+  for (int32_t k = 0; k < K_; ++k) {
+    const int32_t* l = word_ids + (size_t)k * n;
+    for (int32_t i = 0; i < n; ++i) {
+      if (l[i] < -1 || l[i] >= V_) raise(LDA_ERR_INVALID_ARG, "word_ids: id outside [-1, V)");
+      for (int32_t j = 0; l[i] >= 0 && j < i; ++j)
+        if (l[j] == l[i]) raise(LDA_ERR_INVALID_ARG, "word_ids: the same id twice in one topic's list");
+    }
+  }
+  if (P < 0 || P > LDA_DIAG_PROPS_MAX) raise(LDA_ERR_INVALID_ARG, "P must be in [0, LDA_DIAG_PROPS_MAX]");
+  if (P > 0 && !props) raise(LDA_ERR_INVALID_ARG, "null props");
+  for (int32_t i = 0; i < P; ++i)
+    if (!(props[i] > 0.0 && props[i] <= 1.0) || (i > 0 && !(props[i] > props[i - 1])))
+      raise(LDA_ERR_INVALID_ARG, "props must be strictly ascending in (0, 1]");
+  if (!codoc || !doc_stats) raise(LDA_ERR_INVALID_ARG, "null output");
+  ensureShards();
+  const size_t tri = (size_t)K_ * ((size_t)n * (n + 1) / 2), cells = (size_t)K_ * (size_t)(2 + P);
+  std::fill(codoc, codoc + tri, 0);
+  std::fill(doc_stats, doc_stats + cells, 0);
+  std::vector<int32_t> part(tri);
+  std::vector<int64_t> stats(cells);
+  for (auto c : shards_->ctx) {
+    check(lda_topic_codocuments(c, n, word_ids, P, props, part.data(), stats.data()), "lda_topic_codocuments");
+    for (size_t i = 0; i < tri; ++i) codoc[i] += part[i];
+    for (size_t i = 0; i < cells; ++i) doc_stats[i] += stats[i];
+  }
+}
+
+void ParallelTopicModel::topicStatistics(int32_t n, int32_t* word_ids, int32_t* counts, int64_t* totals,
+                                         double* share_sums, uint64_t* sumsq, int64_t* codoc, int64_t* doc_stats) {
+  if (n < 1 || n > LDA_DIAG_WORDS_MAX) raise(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_DIAG_WORDS_MAX]");
+  if (!word_ids) raise(LDA_ERR_INVALID_ARG, "null word_ids");
+  if (!counts || !totals || !share_sums || !sumsq || !codoc || !doc_stats)
+    raise(LDA_ERR_INVALID_ARG, "null output");
+  topWords(n, word_ids, counts);
+  check(lda_topic_word_stats(shards_->ctx[0], n, word_ids, counts, totals, share_sums, sumsq),
+        "lda_topic_word_stats");
+  topicCodocuments(n, word_ids, LDATM_DIAG_PROPS, DIAG_PROPS, codoc, doc_stats);
+}
+
+void diagnosticsFinish(int32_t K, int32_t V, int32_t n, double beta, const int32_t* nwsum, int32_t max_len,
+                       const int64_t* topic_doc_counts, const int32_t* word_ids, const int32_t* counts,
+                       const int64_t* totals, const double* share_sums, const uint64_t* sumsq, const int64_t* codoc,
+                       const int64_t* doc_stats, double* out) {
+  if (K < 1 || V < 1 || max_len < 0) raise(LDA_ERR_INVALID_ARG, "bad sizes");
+  if (n < 1 || n > LDA_DIAG_WORDS_MAX) raise(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_DIAG_WORDS_MAX]");
+  if (!nwsum) raise(LDA_ERR_INVALID_ARG, "null nwsum");
+  if (!topic_doc_counts) raise(LDA_ERR_INVALID_ARG, "null topic_doc_counts");
+  if (!word_ids) raise(LDA_ERR_INVALID_ARG, "null word_ids");
+  if (!counts || !totals || !share_sums || !sumsq || !codoc || !doc_stats)
+    raise(LDA_ERR_INVALID_ARG, "null statistics");
+  if (!out) raise(LDA_ERR_INVALID_ARG, "null output");
+  const size_t L1 = (size_t)max_len + 1, tri = (size_t)n * (n + 1) / 2;
+  const int32_t S = 2 + LDATM_DIAG_PROPS;
+  double N = 0.0;
+  for (int32_t k = 0; k < K; ++k) N += (double)nwsum[k];
+  auto ratio = [](double a, double b) { return b == 0.0 ? 0.0 : a / b; };
+  auto xlog = [](double x, double arg) { return x == 0.0 ? 0.0 : x * std::log(arg); };
+  for (int32_t k = 0; k < K; ++k) {
+    const int64_t* H = topic_doc_counts + (size_t)k * L1;
+    const int64_t* st = doc_stats + (size_t)k * S;
+    const int64_t* C = codoc + (size_t)k * tri;
+    int64_t docs = 0;
+    for (size_t c = 1; c < L1; ++c) docs += H[c];
+    if (docs != st[0])
+      raise(LDA_ERR_INTERNAL, "diagnostics: the topic's document histogram does not add up to its document count");
+    double* o = out + (size_t)k * LDATM_DIAG_COLUMNS;
+    std::fill(o, o + LDATM_DIAG_COLUMNS, 0.0);
+    if (nwsum[k] == 0) continue;
+    const double T = (double)nwsum[k], Dk = (double)st[0];
+    int32_t slot[LDA_DIAG_WORDS_MAX], m = 0;   // the non-empty slots, in list order
+    for (int32_t i = 0; i < n; ++i)
+      if (word_ids[(size_t)k * n + i] >= 0) slot[m++] = i;
+    auto cnt = [&](int32_t i) { return (double)counts[(size_t)k * n + slot[i]]; };
+    auto diag = [&](int32_t i) { return (double)C[(size_t)slot[i] * (slot[i] + 1) / 2 + slot[i]]; };
+    o[LDATM_DIAG_TOKENS] = T;
+    double hsum = 0.0;
+    for (size_t c = 1; c < L1; ++c) hsum += (double)H[c] * ((double)c * std::log((double)c));
+    o[LDATM_DIAG_DOCUMENT_ENTROPY] = std::log(T) - hsum / T;
+    double coh = 0.0;
+    for (int32_t i = 1; i < m; ++i)
+      for (int32_t j = 0; j < i; ++j)
+        coh += std::log(((double)C[(size_t)slot[i] * (slot[i] + 1) / 2 + slot[j]] + beta) / (diag(j) + beta));
+    o[LDATM_DIAG_COHERENCE] = coh;
+    double uni = 0.0, corp = 0.0, csum = 0.0, dsum = 0.0, excl = 0.0;
+    for (int32_t i = 0; i < m; ++i) {
+      const double p = cnt(i) / T;
+      uni += xlog(p, p * (double)V);
+      corp += xlog(p, p / ((double)totals[(size_t)k * n + slot[i]] / N));
+      csum += cnt(i);
+      dsum += diag(i);
+      excl += ((beta + cnt(i)) / ((double)V * beta + T)) / share_sums[(size_t)k * n + slot[i]];
+    }
+    o[LDATM_DIAG_UNIFORM_DIST] = uni;
+    o[LDATM_DIAG_CORPUS_DIST] = corp;
+    o[LDATM_DIAG_EFF_NUM_WORDS] = ratio(T * T, (double)sumsq[k]);
+    double js = 0.0;
+    for (int32_t i = 0; i < m; ++i) {
+      const double p = ratio(cnt(i), csum), q = ratio(diag(i), dsum), mu = (p + q) / 2.0;
+      js += 0.5 * xlog(p, p / mu) + 0.5 * xlog(q, q / mu);
+    }
+    o[LDATM_DIAG_TOKEN_DOC_DIFF] = js;
+    o[LDATM_DIAG_RANK_1_DOCS] = ratio((double)st[1], Dk);
+    o[LDATM_DIAG_ALLOCATION_RATIO] = ratio((double)st[2 + 6], (double)st[2 + 1]);   // 0.5 over 0.02
+    o[LDATM_DIAG_ALLOCATION_COUNT] = ratio((double)st[2 + 5], Dk);                  // 0.3
+    o[LDATM_DIAG_EXCLUSIVITY] = m > 0 ? excl / (double)m : 0.0;
+  }
+}
+
+void ParallelTopicModel::topicDiagnostics(int32_t n, double* out, int32_t* word_ids) {
+  if (n < 1 || n > LDA_DIAG_WORDS_MAX) raise(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_DIAG_WORDS_MAX]");
+  if (!out) raise(LDA_ERR_INVALID_ARG, "null output");
+  ensureShards();
+  const size_t cells = (size_t)K_ * (size_t)n, tri = (size_t)K_ * ((size_t)n * (n + 1) / 2);
+  std::vector<int32_t> ids(cells), counts(cells), nwsum((size_t)K_);
+  std::vector<int64_t> totals(cells), codoc(tri), stats((size_t)K_ * (2 + LDATM_DIAG_PROPS));
+  std::vector<double> shares(cells);
+  std::vector<uint64_t> sumsq((size_t)K_);
+  topicStatistics(n, ids.data(), counts.data(), totals.data(), shares.data(), sumsq.data(), codoc.data(),
+                  stats.data());
+  this->counts(nullptr, nwsum.data());
+  // the shards' topicDocCounts of the current z, summed
+  const size_t L1 = (size_t)max_doc_len_ + 1;
+  std::vector<int64_t> hist((size_t)K_ * L1, 0);
+  std::vector<int32_t> len(L1), part((size_t)K_ * L1);
+  for (auto c : shards_->ctx) {
+    std::fill(len.begin(), len.end(), 0);
+    std::fill(part.begin(), part.end(), 0);
+    check(lda_doc_topic_histograms(c, max_doc_len_, len.data(), part.data()), "lda_doc_topic_histograms");
+    for (size_t i = 0; i < part.size(); ++i) hist[i] += part[i];
+  }
+  diagnosticsFinish(K_, V_, n, beta_, nwsum.data(), max_doc_len_, hist.data(), ids.data(), counts.data(),
+                    totals.data(), shares.data(), sumsq.data(), codoc.data(), stats.data(), out);
+  if (word_ids) std::copy(ids.begin(), ids.end(), word_ids);
+}
+
 std::vector<double> ParallelTopicModel::getTopicProbabilities(int64_t doc) {
   if (doc < 0 || doc >= numDocs()) raise(LDA_ERR_INVALID_ARG, "document index out of range");
   // the document's counts from the device (no copy of z); the arithmetic,
@@ -1794,6 +1940,34 @@ lda_status ldatm_doc_top_topics(ldatm* m, int32_t mtop, int64_t M, const int64_t
 lda_status ldatm_doc_counts(ldatm* m, int64_t M, const int64_t* docs, int32_t* nd) {
   TM_CHECK(m);
   return guard([&] { m->model.docCounts(M, docs, nd); });
+}
+
+lda_status ldatm_topic_codocuments(ldatm* m, int32_t n, const int32_t* word_ids, int32_t P, const double* props,
+                                   int64_t* codoc, int64_t* doc_stats) {
+  TM_CHECK(m);
+  return guard([&] { m->model.topicCodocuments(n, word_ids, P, props, codoc, doc_stats); });
+}
+
+lda_status ldatm_topic_statistics(ldatm* m, int32_t n, int32_t* word_ids, int32_t* counts, int64_t* totals,
+                                  double* share_sums, uint64_t* sumsq, int64_t* codoc, int64_t* doc_stats) {
+  TM_CHECK(m);
+  return guard([&] { m->model.topicStatistics(n, word_ids, counts, totals, share_sums, sumsq, codoc, doc_stats); });
+}
+
+lda_status ldatm_diagnostics_finish(int32_t K, int32_t V, int32_t n, double beta, const int32_t* nwsum,
+                                    int32_t max_len, const int64_t* topic_doc_counts, const int32_t* word_ids,
+                                    const int32_t* counts, const int64_t* totals, const double* share_sums,
+                                    const uint64_t* sumsq, const int64_t* codoc, const int64_t* doc_stats,
+                                    double* out) {
+  return guard([&] {
+    lda_host::diagnosticsFinish(K, V, n, beta, nwsum, max_len, topic_doc_counts, word_ids, counts, totals,
+                                share_sums, sumsq, codoc, doc_stats, out);
+  });
+}
+
+lda_status ldatm_topic_diagnostics(ldatm* m, int32_t n, double* out, int32_t* word_ids) {
+  TM_CHECK(m);
+  return guard([&] { m->model.topicDiagnostics(n, out, word_ids); });
 }
 
 lda_status ldatm_document_topics_text(ldatm* m, double threshold, int32_t max, char* buf, size_t cap,

@@ -27,6 +27,13 @@ class ShardGroup;  // GPU shards + their all-reduce (topic_model.cpp)
 int32_t plan_shards(int32_t num_threads, int32_t num_devices, int64_t num_tokens, int32_t num_types,
                     int32_t num_topics, int64_t num_docs);
 
+// The eleven per-topic diagnostics from the integer statistics (host only,
+// no device; ldatm_diagnostics_finish of lda_topic_model.h states the columns)
+void diagnosticsFinish(int32_t K, int32_t V, int32_t n, double beta, const int32_t* nwsum, int32_t max_len,
+                       const int64_t* topic_doc_counts, const int32_t* word_ids, const int32_t* counts,
+                       const int64_t* totals, const double* share_sums, const uint64_t* sumsq, const int64_t* codoc,
+                       const int64_t* doc_stats, double* out);
+
 class ParallelTopicModel {
  public:
   ParallelTopicModel(int32_t num_topics, double alpha_sum, double beta);
@@ -109,6 +116,19 @@ class ParallelTopicModel {
   // scattered back into the caller's order.  topics / counts [M*mtop]; nd [M*K]
   void docTopTopics(int32_t mtop, int64_t M, const int64_t* docs, int32_t* topics, int32_t* counts);
   void docCounts(int64_t M, const int64_t* docs, int32_t* nd);
+
+  // ---- topic diagnostics --------------------------------
+  // lda_topic_codocuments on every shard with the caller's lists, summed in
+  // int64: codoc [K n(n+1)/2], doc_stats [K (2+P)]
+  void topicCodocuments(int32_t n, const int32_t* word_ids, int32_t P, const double* props, int64_t* codoc,
+                        int64_t* doc_stats);
+  // topWords(n) and lda_topic_word_stats on shard 0, then topicCodocuments
+  // with Mallet's seven proportions (doc_stats [K 9])
+  void topicStatistics(int32_t n, int32_t* word_ids, int32_t* counts, int64_t* totals, double* share_sums,
+                       uint64_t* sumsq, int64_t* codoc, int64_t* doc_stats);
+  // topicStatistics, the shards' topicDocCounts of the current z and
+  // diagnosticsFinish: out [K LDATM_DIAG_COLUMNS]; word_ids [K n] or null
+  void topicDiagnostics(int32_t n, double* out, int32_t* word_ids);
 
   // ---- outputs -------------------------------------------------------
   std::string documentTopics(double threshold, int32_t max);

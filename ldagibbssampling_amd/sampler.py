@@ -433,6 +433,47 @@ class GibbsSampler:
                                           nd.ctypes.data), "lda_doc_counts")
         return nd
 
+    def _word_lists(self, word_ids):
+        """(ids[K, n] int32, n) of K word lists, -1 = an empty slot."""
+        ids = np.ascontiguousarray(word_ids, dtype=np.int32)
+        if ids.ndim != 2 or ids.shape[0] != self.K:
+            raise ValueError("word_ids must be [K, n]")
+        if not 1 <= ids.shape[1] <= capi.DIAG_WORDS_MAX:
+            raise ValueError(f"n must be in [1, {capi.DIAG_WORDS_MAX}]")
+        return ids, ids.shape[1]
+
+    def topic_codocuments(self, word_ids, props=()):
+        """lda_topic_codocuments over this shard's documents and current z.
+        word_ids[K, n] (-1 = empty slot), props ascending in (0, 1].  Returns
+        (codoc[K, n (n + 1) / 2] int32, each topic's packed lower triangle,
+        cell (i, j), j <= i, at i (i + 1) / 2 + j: documents holding both words
+        under that topic; doc_stats[K, 2 + P] int64: documents with the topic,
+        documents it ranks first in, documents where its weight reaches each
+        proportion)."""
+        ids, n = self._word_lists(word_ids)
+        p = np.ascontiguousarray(props, dtype=np.float64).reshape(-1)
+        if len(p) > capi.DIAG_PROPS_MAX:
+            raise ValueError(f"at most {capi.DIAG_PROPS_MAX} props")
+        codoc = np.zeros((self.K, n * (n + 1) // 2), dtype=np.int32)
+        stats = np.zeros((self.K, 2 + len(p)), dtype=np.int64)
+        capi.check(self._L.lda_topic_codocuments(self._h, n, ids.ctypes.data, len(p), p.ctypes.data if len(p) else None,
+                                                 codoc.ctypes.data, stats.ctypes.data), "lda_topic_codocuments")
+        return codoc, stats
+
+    def topic_word_stats(self, word_ids):
+        """lda_topic_word_stats from the global counts: (counts[K, n] int32 =
+        nw[w, k], totals[K, n] int64 = the word's total, share_sums[K, n] fp64 =
+        sum over topics of (beta + nw[w, k']) / (V beta + nwsum[k']),
+        sumsq[K] uint64 = sum over words of nw[w, k]^2); empty slots 0."""
+        ids, n = self._word_lists(word_ids)
+        counts = np.zeros((self.K, n), dtype=np.int32)
+        totals = np.zeros((self.K, n), dtype=np.int64)
+        shares = np.zeros((self.K, n), dtype=np.float64)
+        sumsq = np.zeros(self.K, dtype=np.uint64)
+        capi.check(self._L.lda_topic_word_stats(self._h, n, ids.ctypes.data, counts.ctypes.data, totals.ctypes.data,
+                                                shares.ctypes.data, sumsq.ctypes.data), "lda_topic_word_stats")
+        return counts, totals, shares, sumsq
+
     def heldout_loglik(self, theta, doc_off, words):
         """lda_heldout_loglik: the log likelihood of the scored tokens of Dh
         held-out documents (doc_off[Dh + 1], words) under their topic

@@ -75,6 +75,11 @@ TM_SIGNATURES = {
     "ldatm_top_words": (_i32, [_vp, _i32, _vp, _vp]),
     "ldatm_doc_top_topics": (_i32, [_vp, _i32, C.c_int64, _vp, _vp, _vp]),
     "ldatm_doc_counts": (_i32, [_vp, C.c_int64, _vp, _vp]),
+    "ldatm_topic_codocuments": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "ldatm_topic_statistics": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ldatm_diagnostics_finish": (_i32, [_i32, _i32, _i32, C.c_double, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp, _vp]),
+    "ldatm_topic_diagnostics": (_i32, [_vp, _i32, _vp, _vp]),
     "ldatm_print_document_topics": (_i32, [_vp, C.c_char_p, C.c_double, _i32]),
     "ldatm_document_topics_text": (_i32, [_vp, C.c_double, _i32, _vp, C.c_size_t,
                                           C.POINTER(C.c_size_t)]),
@@ -441,6 +446,56 @@ class ParallelTopicModel:
                                             topics.ctypes.data, cnt.ctypes.data), "docTopTopics")
         return topics, cnt
 
+    # ------------------------------- topic diagnostics
+    def topicCodocuments(self, word_ids, props=()):
+        """ldatm_topic_codocuments: every shard's lda_topic_codocuments with
+        the lists word_ids[K, n] (-1 = empty slot), summed: (codoc[K, n (n + 1)
+        / 2] int64, doc_stats[K, 2 + P] int64)."""
+        ids = np.ascontiguousarray(word_ids, dtype=np.int32)
+        if ids.ndim != 2 or ids.shape[0] != self.numTopics:
+            raise ValueError("word_ids must be [K, n]")
+        n = ids.shape[1]
+        if not 1 <= n <= capi.DIAG_WORDS_MAX:
+            raise ValueError(f"n must be in [1, {capi.DIAG_WORDS_MAX}]")
+        p = np.ascontiguousarray(props, dtype=np.float64).reshape(-1)
+        if len(p) > capi.DIAG_PROPS_MAX:
+            raise ValueError(f"at most {capi.DIAG_PROPS_MAX} props")
+        codoc = np.zeros((self.numTopics, n * (n + 1) // 2), np.int64)
+        stats = np.zeros((self.numTopics, 2 + len(p)), np.int64)
+        _check(self._L.ldatm_topic_codocuments(self._h, n, ids.ctypes.data, len(p), p.ctypes.data if len(p) else None,
+                                               codoc.ctypes.data, stats.ctypes.data), "topicCodocuments")
+        return codoc, stats
+
+    def topicStatistics(self, numTopWords: int = 20) -> dict:
+        """ldatm_topic_statistics: the integer statistics behind the
+        diagnostics for each topic's numTopWords top words, as a dict of
+        word_ids, counts, totals, share_sums [K, n], sumsq [K], codoc
+        [K, n (n + 1) / 2] and doc_stats [K, 9]."""
+        n = int(numTopWords)
+        if not 1 <= n <= capi.DIAG_WORDS_MAX:
+            raise ValueError(f"numTopWords must be in [1, {capi.DIAG_WORDS_MAX}]")
+        K = self.numTopics
+        s = {"word_ids": np.zeros((K, n), np.int32), "counts": np.zeros((K, n), np.int32),
+             "totals": np.zeros((K, n), np.int64), "share_sums": np.zeros((K, n), np.float64),
+             "sumsq": np.zeros(K, np.uint64), "codoc": np.zeros((K, n * (n + 1) // 2), np.int64),
+             "doc_stats": np.zeros((K, 2 + len(DIAG_PROPS)), np.int64)}
+        _check(self._L.ldatm_topic_statistics(self._h, n, *(a.ctypes.data for a in s.values())), "topicStatistics")
+        return s
+
+    def getDiagnostics(self, numTopWords: int = 20) -> "TopicDiagnostics":
+        """Per-topic diagnostics after Mallet's TopicModelDiagnostics, counted on
+        the device (ldatm_topic_diagnostics): a TopicDiagnostics with one array
+        [K] per column of DIAG_COLUMNS."""
+        n = int(numTopWords)
+        if not 1 <= n <= capi.DIAG_WORDS_MAX:
+            raise ValueError(f"numTopWords must be in [1, {capi.DIAG_WORDS_MAX}]")
+        K = self.numTopics
+        out = np.zeros((K, len(DIAG_COLUMNS)), np.float64)
+        ids = np.zeros((K, n), np.int32)
+        _check(self._L.ldatm_topic_diagnostics(self._h, n, out.ctypes.data, ids.ctypes.data), "getDiagnostics")
+        # the triangles themselves, for the same lists (one more document pass)
+        return TopicDiagnostics(self, out, ids, self.topicCodocuments(ids)[0])
+
     def topTopics(self, docs=None, n: int = 10):
         """The n heaviest topics of the documents `docs` (global ids; None =
         all): (topics[M, n] int32, weights[M, n] fp64), weights
@@ -570,6 +625,59 @@ class ParallelTopicModel:
             _check(self._L.ldatm_get_held_out_trace(self._h, it.ctypes.data, ll.ctypes.data, n.value,
                                                     C.byref(n)), "ldatm_get_held_out_trace")
         return list(zip(it.tolist(), ll.tolist()))
+
+
+# LDATM_DIAG_* of lda_topic_model.h: the columns in order, Mallet's proportions
+DIAG_COLUMNS = ("tokens", "document_entropy", "coherence", "uniform_dist", "corpus_dist", "eff_num_words",
+                "token_doc_diff", "rank_1_docs", "allocation_ratio", "allocation_count", "exclusivity")
+DIAG_PROPS = (0.01, 0.02, 0.05, 0.1, 0.2, 0.3, 0.5)
+
+
+def diagnostics_finish(V: int, beta: float, nwsum, topic_doc_counts, word_ids, counts, totals, share_sums, sumsq,
+                       codoc, doc_stats) -> np.ndarray:
+    """ldatm_diagnostics_finish (host only, no device): the columns
+    out[K, len(DIAG_COLUMNS)] from the integer statistics; topic_doc_counts is
+    [K, max_len + 1], doc_stats [K, 9]."""
+    ids = np.ascontiguousarray(word_ids, np.int32)
+    K, n = ids.shape
+    a = [np.ascontiguousarray(nwsum, np.int32), np.ascontiguousarray(topic_doc_counts, np.int64), ids,
+         np.ascontiguousarray(counts, np.int32), np.ascontiguousarray(totals, np.int64),
+         np.ascontiguousarray(share_sums, np.float64), np.ascontiguousarray(sumsq, np.uint64),
+         np.ascontiguousarray(codoc, np.int64), np.ascontiguousarray(doc_stats, np.int64)]
+    if (a[0].shape != (K,) or a[1].ndim != 2 or a[1].shape[0] != K or any(x.shape != (K, n) for x in a[3:6])
+            or a[6].shape != (K,) or a[7].shape != (K, n * (n + 1) // 2) or a[8].shape != (K, 2 + len(DIAG_PROPS))):
+        raise ValueError("statistics of the wrong shape")
+    out = np.zeros((K, len(DIAG_COLUMNS)), np.float64)
+    p = [x.ctypes.data for x in a]
+    _check(load_tm().ldatm_diagnostics_finish(K, int(V), n, float(beta), p[0], a[1].shape[1] - 1, *p[1:],
+                                              out.ctypes.data), "ldatm_diagnostics_finish")
+    return out
+
+
+class TopicDiagnostics:
+    """What ParallelTopicModel.getDiagnostics returns: one array [K] per column
+    of DIAG_COLUMNS (tokens, document_entropy, coherence, ...), topWords (per
+    topic the (word, ...) list the figures were taken over, heaviest first) and
+    codocuments [K, n, n], the symmetric co-document counts of those words
+    under the topic (the diagonal: the word's document frequency)."""
+
+    def __init__(self, model, columns, word_ids, codoc):
+        self.columns = columns
+        self.wordIds = word_ids
+        for i, name in enumerate(DIAG_COLUMNS):
+            setattr(self, name, columns[:, i].copy())
+        name = (lambda w: w) if model.alphabet is None else model.alphabet.lookupObject
+        self.topWords = [[name(int(w)) for w in row if w >= 0] for row in word_ids]
+        K, n = word_ids.shape
+        i, j = np.tril_indices(n)            # row-major lower triangle: i (i + 1) / 2 + j
+        self.codocuments = np.zeros((K, n, n), np.int64)
+        self.codocuments[:, i, j] = codoc
+        self.codocuments[:, j, i] = codoc
+
+    def as_rows(self) -> list:
+        """One dict per topic: 'topic', every column, and 'words'."""
+        return [dict(topic=k, words=self.topWords[k], **{c: float(self.columns[k, i]) for i, c in enumerate(DIAG_COLUMNS)})
+                for k in range(len(self.columns))]
 
 
 class HeldOutResult:
