@@ -430,6 +430,60 @@ lda_status lda_doc_completion(lda_ctx* ctx, int64_t Dh, const int64_t* obs_off, 
                               int32_t thinning, int32_t burn_in, uint64_t seed, double* doc_ll,
                               double* total, double* theta_out);
 
+/* Left-to-right held-out log likelihood: Mallet's MarginalProbEstimator
+ * .evaluateLeftToRight (ParallelTopicModel.getProbEstimator(); Wallach et al.'s
+ * particle estimator of log p(w | model)), on the device against the global
+ * counts this shard holds.  With phi_wk = (nw_wk + beta) *
+ * inv_k, inv_k = 1 / (nwsum_k + V beta), each particle r < num_particles of a
+ * document w_0 .. w_{L-1} starts with nd = 0 and for each limit i = 0 .. L-1
+ *  - if resampling != 0, visits j = 0 .. i-1 in order: takes z_j out of nd,
+ *    draws z_j with weights (nd_k + alpha_k) phi_{w_j,k}, puts it back;
+ *  - takes W = sum_k (nd_k + alpha_k) phi_{w_i,k}, p_r[i] = W / (sum alpha +
+ *    the tokens scored so far), draws z_i with the same weights and adds it.
+ * phat[i] = (p_0[i] + ... + p_{R-1}[i]) / R added in that order, and
+ * doc_ll[d] = sum_i log phat[i].  A token whose type has no training tokens
+ * (lda_infer's empty-row test) is skipped everywhere: no draw, no probability,
+ * no count, not in tokens_scored; an empty or all-skipped document gives 0.0.
+ * All arithmetic is fp64.  A draw with uniform u picks the smallest topic, in
+ * ascending order, whose inclusive prefix of the weights exceeds u W, or the
+ * last topic with a positive weight if none does; u = ((x0 << 21) | (x1 >>
+ * 11)) 2^-53 from Philox4x32-10 with key seed and counter {g lo, g hi, i,
+ * 3 | (r << 8)}, g = the drawn token's index within the call (doc_off[d] -
+ * doc_off[0] + j), i the current limit, stream 3.  No floating-point atomics:
+ * a call repeats bit for bit, and a document's results depend on its tokens,
+ * their indices g and the arguments alone, not on Dh, the other documents,
+ * the chunks or the grid; the first R particles of a call with more are the
+ * particles of a call with R.
+ * total (may be NULL) = doc_ll[0] + ... + doc_ll[Dh-1] added in that order on
+ * the host; tokens_scored (may be NULL) = the tokens not skipped;
+ * token_prob[N] (may be NULL) = phat per token, 0 for a skipped one;
+ * z_out[num_particles * N] (may be NULL), particle-major, = each particle's
+ * topics after its last pass, -1 for a skipped token (N = doc_off[Dh] -
+ * doc_off[0]).
+ * Cost: with resampling a document of L tokens takes L (L + 1) / 2 draws per
+ * particle (L without), each a pass over the word's K counts; hence the
+ * limits below.  Beyond either: LDA_ERR_UNSUPPORTED.
+ * Errors, all checked on the host before any launch: LDA_ERR_INVALID_ARG for
+ * a NULL ctx, doc_off or doc_ll (words may be NULL only without tokens),
+ * Dh < 0, num_particles < 1, a doc_off that is not monotone, or a word id
+ * outside [0, V); LDA_ERR_STATE with a pending delta (call lda_apply first).
+ * Dh = 0 succeeds and touches nothing.
+ * Device scratch is grow-only and kept by the context.  The documents are cut
+ * into chunks of at most 2^20 documents and 2^22 (particle, token) cells (a
+ * single document always fits: 1024 x 4096 = 2^22), so the scratch never
+ * exceeds 16 MiB of topics + 32 MiB of probabilities + 12 bytes per token of
+ * a chunk (ids and phat, <= 48 MiB) + 16 bytes per document of a chunk
+ * (<= 16 MiB) + 8 Kp bytes: 112 MiB + 32 KiB, whatever Dh is.  Waits for the
+ * context's stream. */
+#define LDA_LTR_MAX_PARTICLES 1024
+#define LDA_LTR_MAX_DOC_TOKENS 4096
+lda_status lda_left_to_right(lda_ctx* ctx, int64_t Dh, const int64_t* doc_off, const int32_t* words,
+                             int32_t num_particles, int32_t resampling, uint64_t seed, double* doc_ll,
+                             double* total, int64_t* tokens_scored, double* token_prob, int32_t* z_out);
+/* Test hook: lda_left_to_right cuts its chunks at `cells` (particle, token)
+ * cells instead of 2^22 (0 = the default; a document alone always fits). */
+void lda_debug_ltr_chunk_cells(int64_t cells);
+
 /* The readouts of a trained model, selected on the device.
  *
  * lda_top_words: ParallelTopicModel.printTopWords / displayTopWords' selection
@@ -662,7 +716,8 @@ void lda_debug_fail_host_alloc(int32_t nth);
  * (four 8-bit cells per packed word); 8 -- lda_score_docs.
  * lda_heldout_loglik and lda_doc_completion, then lda_top_words,
  * lda_doc_top_topics and lda_doc_counts, then lda_topic_codocuments and
- * lda_topic_word_stats came later and only add symbols, so the
+ * lda_topic_word_stats, then lda_left_to_right (with its test hook
+ * lda_debug_ltr_chunk_cells) came later and only add symbols, so the
  * version stays 8. */
 #define LDA_ABI_VERSION 8
 const char* lda_version(void);

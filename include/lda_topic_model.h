@@ -21,6 +21,7 @@
  *   held-out log likelihood / perplexity by
  *   document completion, and its trace
  *   during estimate()                            -> ldatm_evaluate / ldatm_heldout_loglik / ldatm_set_held_out
+ *   getProbEstimator().evaluateLeftToRight(...)   -> ldatm_left_to_right
  * Word ids index the model's alphabet (Mallet's Alphabet: insertion order).
  * Errors: lda_status codes of lda_mi355x.h, message in ldatm_last_error().
  */
@@ -352,6 +353,22 @@ lda_status ldatm_heldout_loglik(ldatm* m, int64_t Dh, const double* theta, const
 lda_status ldatm_evaluate(ldatm* m, int64_t Dh, const int64_t* doc_off, const int32_t* words,
                           int32_t num_iterations, int32_t thinning, int32_t burn_in, uint64_t seed,
                           double* doc_ll, double* total, int64_t* tokens_scored, double* theta_out);
+/* ldatm_left_to_right: Mallet's MarginalProbEstimator.evaluateLeftToRight
+ * (ParallelTopicModel.getProbEstimator()) over whole held-out documents, on
+ * the device (lda_left_to_right of lda_mi355x.h; the estimator, its draw and
+ * its random stream there and in DESIGN 9f).  Tokens outside [0, V) are
+ * dropped first, as ldatm_evaluate drops them, and are not counted; a draw's
+ * token index g counts the kept tokens.  Runs on shard 0 for the reason above
+ * (the draws are keyed by a token's index in the call), so the results do not
+ * depend on the number of shards, bit for bit; the model's state is required
+ * and left as ldatm_evaluate requires and leaves it.  doc_ll[Dh]; total
+ * (their sum in document order) and tokens_scored (perplexity = exp(-total /
+ * tokens_scored)) may be NULL.  Errors as lda_left_to_right: num_particles <
+ * 1 INVALID_ARG; more than LDA_LTR_MAX_PARTICLES particles or a document of
+ * more than LDA_LTR_MAX_DOC_TOKENS kept tokens UNSUPPORTED. */
+lda_status ldatm_left_to_right(ldatm* m, int64_t Dh, const int64_t* doc_off, const int32_t* words,
+                               int32_t num_particles, int32_t resampling, uint64_t seed, double* doc_ll,
+                               double* total, int64_t* tokens_scored);
 /* The split ldatm_evaluate makes (host-only): obs_off / sc_off [Dh+1];
  * obs_words / sc_words (may be NULL to get the offsets only) need room for
  * the document's tokens. */

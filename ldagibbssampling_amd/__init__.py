@@ -18,7 +18,8 @@ def __getattr__(name):
     if name == "GibbsSampler":
         from .sampler import GibbsSampler
         return GibbsSampler
-    if name in ("ParallelTopicModel", "TopicInferencer", "InstanceList", "HeldOutEvaluator"):
+    if name in ("ParallelTopicModel", "TopicInferencer", "InstanceList", "HeldOutEvaluator",
+                "MarginalProbEstimator"):
         from . import topic_model
         return getattr(topic_model, name)
     raise AttributeError(name)

@@ -37,6 +37,9 @@ TOP_TOPICS_MAX = 64
 # LDA_DIAG_WORDS_MAX / LDA_DIAG_PROPS_MAX of lda_mi355x.h
 DIAG_WORDS_MAX = 64
 DIAG_PROPS_MAX = 8
+# LDA_LTR_MAX_PARTICLES / LDA_LTR_MAX_DOC_TOKENS of lda_mi355x.h
+LTR_MAX_PARTICLES = 1024
+LTR_MAX_DOC_TOKENS = 4096
 
 
 def score_metric(metric) -> int:
@@ -142,6 +145,9 @@ SIGNATURES = {
     "lda_heldout_loglik": (C.c_int32, [_vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     "lda_doc_completion": (C.c_int32, [_vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_uint64, _vp, _vp, _vp]),
+    "lda_left_to_right": (C.c_int32, [_vp, C.c_int64, _vp, _vp, C.c_int32, C.c_int32, C.c_uint64, _vp, _vp, _vp,
+                                      _vp, _vp]),
+    "lda_debug_ltr_chunk_cells": (None, [C.c_int64]),
     "lda_top_words": (C.c_int32, [_vp, C.c_int32, _vp, _vp]),
     "lda_doc_top_topics": (C.c_int32, [_vp, C.c_int32, C.c_int64, C.c_int64, _vp, _vp, _vp]),
     "lda_doc_counts": (C.c_int32, [_vp, C.c_int64, C.c_int64, _vp, _vp]),

@@ -224,6 +224,13 @@ constexpr int64_t SCORE_CELLS = int64_t(1) << 22;
 // tokens per chunk (32 MiB of ids; a single longer document goes alone)
 constexpr int64_t HELDOUT_THETA_CELLS = int64_t(1) << 22;
 constexpr int64_t HELDOUT_TOKENS = int64_t(1) << 23;
+// lda_left_to_right's chunks: (particle, token) cells (16 MiB of topics, 32
+// MiB of probabilities; LDA_LTR_MAX_PARTICLES x LDA_LTR_MAX_DOC_TOKENS, so a
+// document alone fits) and documents per chunk
+constexpr int64_t LTR_CELLS = int64_t(1) << 22;
+constexpr int64_t LTR_DOCS = int64_t(1) << 20;
+static_assert((int64_t)LDA_LTR_MAX_PARTICLES * LDA_LTR_MAX_DOC_TOKENS <= LTR_CELLS, "a document alone must fit a chunk");
+int64_t g_ltr_cells = 0;   // lda_debug_ltr_chunk_cells (0: LTR_CELLS)
 // lda_top_words' slab pass: at least TOP_WORDS_SLAB_ROWS rows per slab (a
 // slab's list warms up over its first rows), at most TOP_WORDS_WAVES (slab,
 // topic group) waves, which bounds the slab lists at TOP_WORDS_WAVES * 64 * n
@@ -320,6 +327,13 @@ struct lda_ctx {
   int32_t* held_words = nullptr;
   int64_t* held_off = nullptr;
   size_t held_cap[5] = {};
+  // lda_left_to_right: grow-only scratch -- the chunk's particle-major topics
+  // and probabilities [R x Nc], its token ids, phat [Nc], offsets [Dc + 1],
+  // results [Dc] (inv is held_inv)
+  int32_t *ltr_z = nullptr, *ltr_words = nullptr;
+  double *ltr_p = nullptr, *ltr_phat = nullptr, *ltr_ll = nullptr;
+  int64_t* ltr_off = nullptr;
+  size_t ltr_cap[6] = {};
   // lda_top_words / lda_doc_counts / lda_doc_top_topics: grow-only scratch --
   // the slab lists [slabs x Kp x n keys], the int32 results of a chunk and
   // the chunk's document ids
@@ -482,6 +496,7 @@ struct lda_ctx {
                     (void*)inf_z, (void*)inf_acc, (void*)inf_q, (void*)inf_doff, (void*)inf_range,
                     (void*)score_theta, (void*)score_out, (void*)score_docs,
                     (void*)held_theta, (void*)held_ll, (void*)held_inv, (void*)held_words, (void*)held_off,
+                    (void*)ltr_z, (void*)ltr_words, (void*)ltr_p, (void*)ltr_phat, (void*)ltr_ll, (void*)ltr_off,
                     (void*)ro_lists, (void*)ro_out, (void*)ro_docs,
                     (void*)dg_ids, (void*)dg_table, (void*)dg_out, (void*)dg_shares,
                     (void*)perm, (void*)items, (void*)warm.range_doc, (void*)steady.range_doc,
@@ -2191,6 +2206,27 @@ lda_status lda_row_stats(lda_ctx* c, double* mean_row_nnz) {
   });
 }
 
+namespace {
+
+// c->word_totals: the row totals of the global snapshot (saturating at Kp),
+// computed once per snapshot -- TopicInferencer's empty-row test
+lda_status refresh_word_totals(lda_ctx* c) {
+  if (c->totals_gen == c->apply_gen) return LDA_OK;
+  int32_t* caps = nullptr;
+  HIP_TRY(dalloc(&caps, c->V));
+  c->word_totals.assign((size_t)c->V, 0);
+  hipError_t e = lda::launch_row_caps(c->nw, c->V, c->Kp, caps, c->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(c->word_totals.data(), caps, sizeof(int32_t) * c->V, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(caps);
+  HIP_TRY(e);
+  c->totals_gen = c->apply_gen;
+  return LDA_OK;
+}
+
+}  // namespace
+
 lda_status lda_infer(lda_ctx* c, int64_t Dh, const int64_t* doc_off, const int32_t* words_in,
                      int32_t n_iter, int32_t thin, int32_t burn_in, uint64_t seed, double* theta) {
   return lda_abi::guarded([&]() -> lda_status {
@@ -2207,18 +2243,7 @@ lda_status lda_infer(lda_ctx* c, int64_t Dh, const int64_t* doc_off, const int32
   // TopicInferencer skips tokens whose type has no training tokens (an empty
   // typeTopicCounts row): drop them here (row totals of the global snapshot,
   // computed once per snapshot)
-  if (c->totals_gen != c->apply_gen) {
-    int32_t* caps = nullptr;
-    HIP_TRY(dalloc(&caps, c->V));
-    c->word_totals.assign((size_t)c->V, 0);
-    hipError_t e = lda::launch_row_caps(c->nw, c->V, c->Kp, caps, c->stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(c->word_totals.data(), caps, sizeof(int32_t) * c->V, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(caps);
-    HIP_TRY(e);
-    c->totals_gen = c->apply_gen;
-  }
+  if (lda_status s = refresh_word_totals(c); s != LDA_OK) return s;
   std::vector<int64_t> off(Dh + 1);
   std::vector<int32_t> kept;
   kept.reserve((size_t)N_in);
@@ -2856,6 +2881,126 @@ lda_status lda_doc_completion(lda_ctx* c, int64_t Dh, const int64_t* obs_off, co
       s != LDA_OK)
     return s;
   return lda_heldout_loglik(c, Dh, theta, sc_off, sc_words, doc_ll, total);
+  });
+}
+
+void lda_debug_ltr_chunk_cells(int64_t cells) { g_ltr_cells = cells > 0 ? cells : 0; }
+
+lda_status lda_left_to_right(lda_ctx* c, int64_t Dh, const int64_t* doc_off, const int32_t* words_in,
+                             int32_t R, int32_t resampling, uint64_t seed, double* doc_ll, double* total,
+                             int64_t* tokens_scored, double* token_prob, int32_t* z_out) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (Dh < 0) return fail(LDA_ERR_INVALID_ARG, "bad sizes");
+  if (R < 1) return fail(LDA_ERR_INVALID_ARG, "num_particles must be at least 1");
+  if (c->pending) return fail(LDA_ERR_STATE, "left-to-right evaluation with a pending delta: call lda_apply first");
+  if (Dh == 0) return LDA_OK;
+  if (!doc_off || !doc_ll) return fail(LDA_ERR_INVALID_ARG, "null argument");
+  if (lda_status s = check_heldout_docs(c, Dh, doc_off, words_in); s != LDA_OK) return s;
+  if (R > LDA_LTR_MAX_PARTICLES) return fail(LDA_ERR_UNSUPPORTED, "more than LDA_LTR_MAX_PARTICLES particles");
+  for (int64_t d = 0; d < Dh; ++d)
+    if (doc_off[d + 1] - doc_off[d] > LDA_LTR_MAX_DOC_TOKENS)
+      return fail(LDA_ERR_UNSUPPORTED, "document longer than LDA_LTR_MAX_DOC_TOKENS tokens");
+  HIP_TRY(hipSetDevice(c->device));
+  if (lda_status s = refresh_word_totals(c); s != LDA_OK) return s;
+  const int64_t first = doc_off[0], N = doc_off[Dh] - first;
+  // the ids as the kernels read them: -1 for a type without training tokens
+  std::vector<int32_t> ids = host_vector<int32_t>((size_t)N);
+  int64_t scored = 0;
+  for (int64_t i = 0; i < N; ++i) {
+    const bool keep = c->word_totals[(size_t)words_in[i]] > 0;
+    ids[(size_t)i] = keep ? words_in[i] : -1;
+    scored += keep;
+  }
+  // chunks of documents: at most LTR_DOCS documents and `cells` (particle,
+  // token) cells each (a single larger document goes alone)
+  const int64_t cells = g_ltr_cells > 0 ? g_ltr_cells : LTR_CELLS;
+  const int64_t tok_cap = std::max<int64_t>(1, cells / R);
+  std::vector<int64_t> cut(1, 0);
+  int64_t max_tokens = 1, max_docs = 1;
+  for (int64_t d0 = 0; d0 < Dh;) {
+    int64_t d1 = d0 + 1;
+    while (d1 < Dh && d1 - d0 < LTR_DOCS && doc_off[d1 + 1] - doc_off[d0] <= tok_cap) ++d1;
+    max_tokens = std::max(max_tokens, doc_off[d1] - doc_off[d0]);
+    max_docs = std::max(max_docs, d1 - d0);
+    cut.push_back(d1);
+    d0 = d1;
+  }
+  hipError_t e = hipSuccess;
+  auto chk = [&](hipError_t x) {
+    if (e == hipSuccess) e = x;
+  };
+  auto need = [&](auto*& ptr, size_t n, size_t& cap) {
+    if (e != hipSuccess || n <= cap) return;
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr;
+    cap = 0;
+    chk(dalloc(&ptr, n));
+    if (e == hipSuccess) cap = n;
+  };
+  need(c->ltr_z, (size_t)R * max_tokens, c->ltr_cap[0]);
+  need(c->ltr_p, (size_t)R * max_tokens, c->ltr_cap[1]);
+  need(c->ltr_words, (size_t)max_tokens, c->ltr_cap[2]);
+  need(c->ltr_phat, (size_t)max_tokens, c->ltr_cap[3]);
+  need(c->ltr_off, (size_t)max_docs + 1, c->ltr_cap[4]);
+  need(c->ltr_ll, (size_t)max_docs, c->ltr_cap[5]);
+  need(c->held_inv, (size_t)c->Kp, c->held_cap[2]);
+  HIP_TRY(e);
+  HIP_TRY(lda::launch_heldout_inv(c->nwsum, (double)c->V * c->beta, c->K, c->Kp, c->held_inv, c->stream));
+  double A = 0.0;
+  for (int k = 0; k < c->K; ++k) A += c->alpha[(size_t)k];
+  std::vector<int64_t> off = host_vector<int64_t>((size_t)max_docs + 1);
+  for (size_t ch = 0; ch + 1 < cut.size(); ++ch) {
+    const int64_t d0 = cut[ch], dn = cut[ch + 1] - d0;
+    const int64_t w0 = doc_off[d0] - first, wn = doc_off[d0 + dn] - first - w0;
+    if (wn == 0) {   // empty documents only: nothing to launch
+      for (int64_t d = 0; d < dn; ++d) doc_ll[d0 + d] = 0.0;
+      continue;
+    }
+    for (int64_t d = 0; d <= dn; ++d) off[(size_t)d] = doc_off[d0 + d] - first - w0;
+    HIP_TRY(hipMemcpyAsync(c->ltr_off, off.data(), sizeof(int64_t) * (size_t)(dn + 1), hipMemcpyHostToDevice,
+                           c->stream));
+    HIP_TRY(hipMemcpyAsync(c->ltr_words, ids.data() + w0, sizeof(int32_t) * (size_t)wn, hipMemcpyHostToDevice,
+                           c->stream));
+    lda::LeftToRightArgs a{};
+    a.nw = c->nw;
+    a.inv = c->held_inv;
+    a.alpha = c->alpha_d;
+    a.doc_off = c->ltr_off;
+    a.words = c->ltr_words;
+    a.z = c->ltr_z;
+    a.p = c->ltr_p;
+    a.phat = c->ltr_phat;
+    a.ll = c->ltr_ll;
+    a.D = dn;
+    a.N = wn;
+    a.g0 = w0;
+    a.R = R;
+    a.resampling = resampling != 0;
+    a.K = c->K;
+    a.Kp = c->Kp;
+    a.beta = c->beta;
+    a.A = A;
+    a.k0 = (uint32_t)seed;
+    a.k1 = (uint32_t)(seed >> 32);
+    HIP_TRY(lda::launch_left_to_right(a, c->stream));
+    HIP_TRY(lda::launch_ltr_reduce(a, c->stream));
+    HIP_TRY(hipMemcpyAsync(doc_ll + d0, c->ltr_ll, sizeof(double) * (size_t)dn, hipMemcpyDeviceToHost, c->stream));
+    if (token_prob)
+      HIP_TRY(hipMemcpyAsync(token_prob + w0, c->ltr_phat, sizeof(double) * (size_t)wn, hipMemcpyDeviceToHost,
+                             c->stream));
+    if (z_out)
+      HIP_TRY(hipMemcpy2DAsync(z_out + w0, sizeof(int32_t) * (size_t)N, c->ltr_z, sizeof(int32_t) * (size_t)wn,
+                               sizeof(int32_t) * (size_t)wn, (size_t)R, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));   // the scratch (and off) is reused by the next chunk
+  }
+  if (total) {
+    double t = 0.0;
+    for (int64_t d = 0; d < Dh; ++d) t += doc_ll[d];
+    *total = t;
+  }
+  if (tokens_scored) *tokens_scored = scored;
+  return LDA_OK;
   });
 }
 

@@ -11,6 +11,7 @@ namespace lda {
 constexpr uint32_t STREAM_SAMPLE = 0u;
 constexpr uint32_t STREAM_INIT = 1u;
 constexpr uint32_t STREAM_INFER = 2u;
+constexpr uint32_t STREAM_LTR = 3u;     // lda_left_to_right; the particle sits in bits 8 and up
 
 // Row-prefetch depth of the sampler per C = Kp/64 (tokens in flight per wave;
 // C = 8: P = 3 is +1% over 2 on C4 once the pipeline waits vmcnt(P-1), P = 4
@@ -350,6 +351,30 @@ struct DocCompletionArgs {
 hipError_t launch_heldout_inv(const int32_t* nwsum, double vbeta, int32_t K, int32_t Kp, double* inv,
                               hipStream_t st);
 hipError_t launch_doc_completion(const DocCompletionArgs& a, int blocks, hipStream_t st);
+// lda_left_to_right: k_left_to_right, one wave per (document,
+// particle) of a chunk, job = d * R + r, writes the particle's topics z[r * N +
+// t] and probabilities p[r * N + t]; k_ltr_reduce, one wave per document,
+// averages them into phat[N] and sums the logs into ll[D].  words holds -1 for
+// a skipped token (a type without training tokens): no draw, z = -1, p = 0.
+// The uniform of a draw is Philox counter {g lo, g hi, limit, STREAM_LTR |
+// (r << 8)} with g = g0 + the token's index in the chunk.
+struct LeftToRightArgs {
+  const int32_t* nw;        // [V * Kp]
+  const double* inv;        // [Kp] (launch_heldout_inv)
+  const double* alpha;      // [K]
+  const int64_t* doc_off;   // [D + 1] into words
+  const int32_t* words;     // [N], -1 = skipped
+  int32_t* z;               // [R * N]
+  double* p;                // [R * N]
+  double* phat;             // [N]
+  double* ll;               // [D]
+  int64_t D, N, g0;
+  int32_t R, resampling, K, Kp;
+  double beta, A;           // A = alpha[0] + ... + alpha[K-1], added in that order
+  uint32_t k0, k1;          // Philox key (seed)
+};
+hipError_t launch_left_to_right(const LeftToRightArgs& a, hipStream_t st);
+hipError_t launch_ltr_reduce(const LeftToRightArgs& a, hipStream_t st);
 // range workers per block of the sampler kernel used for (C, sampler): 4
 // waves, 16 for the large-K sparse kernel (C >= 32), 8 for the half-wave
 // dense kernel (4 waves x 2 halves)

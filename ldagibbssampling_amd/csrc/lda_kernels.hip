@@ -3671,6 +3671,323 @@ __global__ __launch_bounds__(256) void k_doc_completion(const DocCompletionArgs 
   }
 }
 
+// ------------------------------------------- left-to-right
+// The uniform of one draw: Philox4x32-10 words 0 and 1 of counter {g lo, g hi,
+// limit, STREAM_LTR | (r << 8)} as a 53-bit fraction.
+__device__ __forceinline__ double ltr_uniform(uint64_t g, uint32_t limit, uint32_t r, uint32_t k0, uint32_t k1) {
+  uint32_t c0 = (uint32_t)g, c1 = (uint32_t)(g >> 32), c2 = limit, c3 = STREAM_LTR | (r << 8);
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    if (i > 0) {
+      k0 += PHILOX_W0;
+      k1 += PHILOX_W1;
+    }
+    const uint32_t hi0 = __umulhi(PHILOX_M0, c0), lo0 = PHILOX_M0 * c0;
+    const uint32_t hi1 = __umulhi(PHILOX_M1, c2), lo1 = PHILOX_M1 * c2;
+    const uint32_t n0 = hi1 ^ c1 ^ k0;
+    const uint32_t n2 = hi0 ^ c3 ^ k1;
+    c0 = n0;
+    c1 = lo1;
+    c2 = n2;
+    c3 = lo0;
+  }
+  return (double)(((uint64_t)c0 << 21) | (uint64_t)(c1 >> 11)) * 0x1p-53;
+}
+
+__device__ __forceinline__ double readlane_d(double v, int l) {
+  const uint64_t b = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, l);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), l);
+  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+
+template <int CTRL, int ROW_MASK, bool BOUND>
+__device__ __forceinline__ double dpp_mov_d(double v) {
+  const uint64_t b = __builtin_bit_cast(uint64_t, v);
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)b, CTRL, ROW_MASK, 0xf, BOUND);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(b >> 32), CTRL, ROW_MASK, 0xf, BOUND);
+  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+// Inclusive fp64 wavefront scan in wave_incl_scan's order: x_l += x_{l-o}
+// inside the 16-lane rows for o = 1, 2, 4, 8 (row_shr; a source outside the
+// row reads 0), then rows 1 and 3 add lane 15 of the row before them
+// (row_bcast:15), then rows 2 and 3 add lane 31 (row_bcast:31).  Lanes a step
+// does not reach add +0.0, which changes no bit of a non-negative sum.
+__device__ __forceinline__ double wave_incl_scan_d(double x) {
+  x += dpp_mov_d<0x111, 0xf, true>(x);
+  x += dpp_mov_d<0x112, 0xf, true>(x);
+  x += dpp_mov_d<0x114, 0xf, true>(x);
+  x += dpp_mov_d<0x118, 0xf, true>(x);
+  x += dpp_mov_d<0x142, 0xa, false>(x);
+  x += dpp_mov_d<0x143, 0xc, false>(x);
+  return x;
+}
+
+// alpha and inv of a lane's topics live in registers up to this C; above it
+// they are read from memory in the draw (8 Kp bytes each, cache resident)
+constexpr int LTR_REG_C = 8;
+constexpr int ltr_reg(int C) { return C <= LTR_REG_C ? C : 1; }
+
+// A particle's document-topic counts of the lane's C topics: registers below
+// LTR_LDS_C topics per lane, above that the wave's own LDS (as int4 blocks,
+// block b of lane l at int4 index b * 64 + l: conflict-free 16-byte reads).
+// Every cell is written and read by its owning lane alone, so there is no
+// hand-off between lanes to order.
+constexpr int LTR_LDS_C = 32;
+template <int C, bool LDS = (C >= LTR_LDS_C)>
+struct LtrNd;
+template <int C>
+struct LtrNd<C, false> {
+  int32_t v[C];
+  int k0;
+  __device__ __forceinline__ LtrNd(int32_t*, int lane) : k0(lane * C) {}
+  __device__ __forceinline__ void clear() {
+#pragma unroll
+    for (int c = 0; c < C; ++c) v[c] = 0;
+  }
+  __device__ __forceinline__ void add(int k, int by) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) v[c] += k == k0 + c ? by : 0;
+  }
+  template <int B>
+  __device__ __forceinline__ void get(int b, int32_t (&o)[B]) const {
+#pragma unroll
+    for (int j = 0; j < B; ++j) o[j] = v[b * B + j];
+  }
+};
+template <int C>
+struct LtrNd<C, true> {
+  int32_t* s;   // the wave's [64 C]
+  int lane;
+  __device__ __forceinline__ LtrNd(int32_t* wave_lds, int l) : s(wave_lds), lane(l) {}
+  __device__ __forceinline__ void clear() {
+#pragma unroll
+    for (int b = 0; b < C / 4; ++b) reinterpret_cast<int4*>(s)[b * 64 + lane] = make_int4(0, 0, 0, 0);
+  }
+  __device__ __forceinline__ void add(int k, int by) {
+    const int l = k / C, c = k % C;
+    if (lane == l) s[((c >> 2) * 64 + l) * 4 + (c & 3)] += by;
+  }
+  template <int B>
+  __device__ __forceinline__ void get(int b, int32_t (&o)[B]) const {
+    static_assert(B == 4, "int4 blocks");
+    const int4 x = reinterpret_cast<const int4*>(s)[b * 64 + lane];
+    o[0] = x.x;
+    o[1] = x.y;
+    o[2] = x.z;
+    o[3] = x.w;
+  }
+};
+
+// THE draw of the estimator (both modes, resampled and new tokens): topic k
+// of lane l = k / C weighs w_k = ((double) nd_k + alpha_k) * (((double)
+// nw_wk + beta) * inv_k), 0 past K.  p_c = w_{lC} + ... + w_{lC+c} added in
+// that order from 0; S = p_{C-1}; T = the inclusive scan of S over the lanes
+// (wave_incl_scan_d's order), E_l = T_{l-1} (0 for lane 0), W = T_63.  The
+// inclusive prefix of topic lC + c is E_l + p_c; with t = u W the draw is the
+// smallest topic whose prefix exceeds t: the first lane with E + S > t, then
+// its first c.  If no prefix exceeds t, the last topic with a positive weight.  The weights are computed twice from the same operands (the
+// second time for the prefixes), so both passes see the same bits.  Up to
+// LTR_REG_C topics per lane the caller has loaded the lane's row slice into
+// `pre` (ahead of time: the words are known before the draws); above, the
+// slice is read from `row` block by block.
+template <int C>
+__device__ __forceinline__ int ltr_draw(const int32_t* __restrict__ row, const int32_t (&pre)[ltr_reg(C)],
+                                        const LtrNd<C>& nd,
+                                        const double (&al)[ltr_reg(C)], const double (&iv)[ltr_reg(C)],
+                                        const double* __restrict__ alpha, const double* __restrict__ inv, int K,
+                                        int lane, double beta, double u, double& W) {
+  constexpr bool REG = C <= LTR_REG_C;
+  constexpr int B = C < 4 ? C : 4;
+  const int k0 = lane * C;
+  auto block = [&](int b, double (&w)[B]) {
+    int32_t v[B], n[B];
+    if constexpr (REG) {
+#pragma unroll
+      for (int j = 0; j < B; ++j) v[j] = pre[b * B + j];
+    } else {
+      load_row_slice<B>(row + k0 + b * B, v);
+    }
+    nd.template get<B>(b, n);
+#pragma unroll
+    for (int j = 0; j < B; ++j) {
+      const int c = b * B + j;
+      double a, q;
+      if constexpr (REG) {
+        a = al[c];
+        q = iv[c];
+      } else {
+        a = k0 + c < K ? alpha[k0 + c] : 0.0;
+        q = inv[k0 + c];
+      }
+      w[j] = ((double)n[j] + a) * (((double)v[j] + beta) * q);
+    }
+  };
+  double S = 0.0;
+#pragma unroll
+  for (int b = 0; b < C / B; ++b) {
+    double w[B];
+    block(b, w);
+#pragma unroll
+    for (int j = 0; j < B; ++j) S += w[j];
+  }
+  const double T = wave_incl_scan_d(S);
+  double E = __shfl_up(T, 1);
+  if (lane == 0) E = 0.0;
+  W = readlane_d(T, 63);
+  const double t = u * W;
+  const uint64_t m = __ballot(E + S > t);
+  double p = 0.0;
+  int first = -1, last = -1;
+#pragma unroll
+  for (int b = 0; b < C / B; ++b) {
+    double w[B];
+    block(b, w);
+#pragma unroll
+    for (int j = 0; j < B; ++j) {
+      p += w[j];
+      if (first < 0 && E + p > t) first = b * B + j;
+      if (w[j] > 0.0) last = b * B + j;
+    }
+  }
+  if (m != 0) {
+    const int l = uniform_i(__builtin_ctzll(m));
+    return l * C + readlane_i(first, l);
+  }
+  const uint64_t mp = __ballot(last >= 0);
+  if (mp == 0) return K - 1;
+  const int l = uniform_i(63 - __builtin_clzll(mp));
+  return l * C + readlane_i(last, l);
+}
+
+// lda_left_to_right: one wave per (document, particle), job = d * R + r.  Lane
+// l owns topics [l C, (l + 1) C) and keeps the particle's nd of them (LtrNd:
+// registers, or the wave's LDS from LTR_LDS_C on).  The document goes in 64-token chunks aligned at its start: lane
+// t of a chunk holds the token's word, topic and (in a resampling pass)
+// uniform, the word goes to the scalar unit by readlane so the row base is
+// scalar, and token j's topic is always stored and loaded by lane j % 64, so
+// the wave's own program order carries it from one pass to the next.  A
+// skipped token (word -1) takes no draw; its z is -1 and its p is 0.
+template <int C>
+__global__ __launch_bounds__(256) void k_left_to_right(const LeftToRightArgs a) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int32_t* __restrict__ nw = a.nw;
+  const int32_t* __restrict__ words = a.words;
+  const double* __restrict__ alpha = a.alpha;
+  const double* __restrict__ inv = a.inv;
+  const int k0 = lane * C;
+  constexpr bool REG = C <= LTR_REG_C;
+  constexpr int RC = ltr_reg(C);
+  const int64_t jobs = a.D * (int64_t)a.R;
+  if ((int64_t)blockIdx.x * 4 + wid >= jobs) return;   // nothing to do: no memory touched
+  int32_t* nd_lds = nullptr;
+  if constexpr (C >= LTR_LDS_C) {
+    __shared__ __attribute__((aligned(16))) int32_t nd_block[4 * 64 * C];
+    nd_lds = nd_block + wid * 64 * C;
+  }
+  LtrNd<C> nd(nd_lds, lane);
+  double al[ltr_reg(C)], iv[ltr_reg(C)];
+  if constexpr (C <= LTR_REG_C) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      al[c] = k0 + c < a.K ? alpha[k0 + c] : 0.0;
+      iv[c] = inv[k0 + c];
+    }
+  } else {
+    al[0] = iv[0] = 0.0;
+  }
+  for (int64_t job = uniform_l((int64_t)blockIdx.x * 4 + wid); job < jobs; job += (int64_t)gridDim.x * 4) {
+    const int64_t d = job / a.R;
+    const uint32_t r = (uint32_t)(job - d * a.R);
+    const int64_t t0 = a.doc_off[d];
+    const int L = (int)(a.doc_off[d + 1] - t0);
+    if (L <= 0) continue;
+    int32_t* zr = a.z + (int64_t)r * a.N + t0;
+    double* pr = a.p + (int64_t)r * a.N + t0;
+    const uint64_t g0 = (uint64_t)(a.g0 + t0);
+    nd.clear();
+    double so_far = 0.0;
+    int wcur = -1;
+    // a lane's slice of a word's row (a skipped word reads row 0, unused)
+    auto row_of = [&](int w) { return nw + (size_t)(w < 0 ? 0 : w) * a.Kp; };
+    auto preload = [&](int w, int32_t (&v)[RC]) {
+      if constexpr (REG) load_row_slice<C>(row_of(w) + k0, v);
+      else v[0] = 0;
+    };
+    for (int i = 0; i < L; ++i) {
+      if ((i & 63) == 0) wcur = i + lane < L ? words[t0 + i + lane] : -1;
+      const int w = readlane_i(wcur, i & 63);
+      int32_t vi[RC];
+      preload(w, vi);   // the new token's row: in flight over the resampling pass
+      if (a.resampling) {
+        for (int base = 0; base < i; base += 64) {
+          const int n = i - base < 64 ? i - base : 64;   // wave-uniform
+          const int wv = lane < n ? words[t0 + base + lane] : -1;
+          int zv = lane < n ? zr[base + lane] : -1;
+          const double uv = ltr_uniform(g0 + (uint64_t)(base + lane), (uint32_t)i, r, a.k0, a.k1);
+          int32_t v[RC];
+          preload(readlane_i(wv, 0), v);
+          for (int t = 0; t < n; ++t) {
+            int32_t vn[RC];
+            preload(readlane_i(wv, t + 1 < n ? t + 1 : t), vn);   // the next token's row, ahead of this draw
+            const int wt = readlane_i(wv, t);
+            if (wt >= 0) {
+              nd.add(readlane_i(zv, t), -1);
+              double W;
+              const int zn = ltr_draw<C>(row_of(wt), v, nd, al, iv, alpha, inv, a.K, lane, a.beta,
+                                         readlane_d(uv, t), W);
+              nd.add(zn, 1);
+              if (lane == t) zv = zn;
+            }
+#pragma unroll
+            for (int c = 0; c < RC; ++c) v[c] = vn[c];
+          }
+          if (lane < n) zr[base + lane] = zv;
+        }
+      }
+      int zn = -1;
+      double p = 0.0;
+      if (w >= 0) {
+        double W;
+        zn = ltr_draw<C>(row_of(w), vi, nd, al, iv, alpha, inv, a.K, lane, a.beta,
+                         ltr_uniform(g0 + (uint64_t)i, (uint32_t)i, r, a.k0, a.k1), W);
+        p = W / (a.A + so_far);
+        so_far += 1.0;
+        nd.add(zn, 1);
+      }
+      if (lane == (i & 63)) {
+        zr[i] = zn;
+        pr[i] = p;
+      }
+    }
+  }
+}
+
+// lda_left_to_right: phat[t] = (p_0[t] + ... + p_{R-1}[t]) / R added in that
+// order, 0 for a skipped token; ll[d] = the sum of log phat over the
+// document's scored tokens: lane l adds tokens l, l + 64, ... of the document
+// in ascending order, then the lanes combine in wave_sum_d's butterfly.  One
+// wave per document.
+__global__ __launch_bounds__(256) void k_ltr_reduce(const LeftToRightArgs a) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  for (int64_t d = (int64_t)blockIdx.x * 4 + wid; d < a.D; d += (int64_t)gridDim.x * 4) {
+    const int64_t t0 = a.doc_off[d], t1 = a.doc_off[d + 1];
+    double ll = 0.0;
+    for (int64_t t = t0 + lane; t < t1; t += 64) {
+      double ph = 0.0;
+      if (a.words[t] >= 0) {
+        double s = 0.0;
+        for (int r = 0; r < a.R; ++r) s += a.p[(int64_t)r * a.N + t];
+        ph = s / (double)a.R;
+        ll += log(ph);
+      }
+      a.phat[t] = ph;
+    }
+    ll = wave_sum_d(ll);
+    if (lane == 0) a.ll[d] = ll;
+  }
+}
+
 // Word part: sum over nonzero nw cells of logGammaStirling(beta + count).
 __global__ __launch_bounds__(256) void k_ll_words(const int32_t* __restrict__ nw, int64_t V,
                                                   int32_t K, int32_t Kp, double beta,
@@ -4467,6 +4784,36 @@ hipError_t launch_doc_completion(const DocCompletionArgs& a, int blocks, hipStre
     case 64: return launch_doc_completion_t<64>(a, blocks, st);
     default: return hipErrorInvalidValue;
   }
+}
+
+template <int C>
+static hipError_t launch_left_to_right_t(const LeftToRightArgs& a, int blocks, hipStream_t st) {
+  hipLaunchKernelGGL(k_left_to_right<C>, dim3(blocks), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_left_to_right(const LeftToRightArgs& a, hipStream_t st) {
+  if (a.D <= 0 || a.N <= 0 || a.R <= 0) return hipSuccess;
+  // a block per four jobs: the hardware hands blocks out as waves finish,
+  // which evens out documents of unequal length
+  const int blocks = (int)std::min<int64_t>((a.D * a.R + 3) / 4, int64_t(1) << 20);
+  switch (a.Kp / 64) {
+    case 1: return launch_left_to_right_t<1>(a, blocks, st);
+    case 2: return launch_left_to_right_t<2>(a, blocks, st);
+    case 4: return launch_left_to_right_t<4>(a, blocks, st);
+    case 8: return launch_left_to_right_t<8>(a, blocks, st);
+    case 16: return launch_left_to_right_t<16>(a, blocks, st);
+    case 32: return launch_left_to_right_t<32>(a, blocks, st);
+    case 64: return launch_left_to_right_t<64>(a, blocks, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+hipError_t launch_ltr_reduce(const LeftToRightArgs& a, hipStream_t st) {
+  if (a.D <= 0) return hipSuccess;
+  const int blocks = (int)std::min<int64_t>((a.D + 3) / 4, 8192);
+  hipLaunchKernelGGL(k_ltr_reduce, dim3(blocks), dim3(256), 0, st, a);
+  return hipGetLastError();
 }
 
 hipError_t launch_ll_words(const int32_t* nw, int64_t V, int32_t K, int32_t Kp, double beta,

@@ -1632,6 +1632,30 @@ double ParallelTopicModel::evaluate(int64_t Dh, const int64_t* doc_off, const in
   return total;
 }
 
+double ParallelTopicModel::leftToRight(int64_t Dh, const int64_t* doc_off, const int32_t* words,
+                                       int32_t num_particles, int32_t resampling, uint64_t seed, double* doc_ll,
+                                       int64_t* tokens_scored) {
+  ensureShards();
+  if (Dh < 0 || (Dh > 0 && (!doc_off || !doc_ll))) raise(LDA_ERR_INVALID_ARG, "bad documents");
+  for (int64_t d = 1; d <= Dh; ++d)
+    if (doc_off[d] < doc_off[d - 1]) raise(LDA_ERR_INVALID_ARG, "doc_off not monotone");
+  if (Dh > 0 && doc_off[Dh] > doc_off[0] && !words) raise(LDA_ERR_INVALID_ARG, "words is null");
+  std::vector<int64_t> off((size_t)Dh + 1, 0);
+  std::vector<int32_t> kept;
+  for (int64_t d = 0; d < Dh; ++d) {
+    for (int64_t i = doc_off[d] - doc_off[0]; i < doc_off[d + 1] - doc_off[0]; ++i)
+      if (words[i] >= 0 && words[i] < V_) kept.push_back(words[i]);
+    off[(size_t)d + 1] = (int64_t)kept.size();
+  }
+  double total = 0.0;
+  int64_t scored = 0;
+  check(lda_left_to_right(shards_->ctx[0], Dh, off.data(), kept.empty() ? nullptr : kept.data(), num_particles,
+                          resampling, seed, doc_ll, &total, &scored, nullptr, nullptr),
+        "lda_left_to_right");
+  if (tokens_scored) *tokens_scored = scored;
+  return total;
+}
+
 void ParallelTopicModel::setHeldOut(int64_t Dh, const int64_t* doc_off, const int32_t* words, int32_t interval,
                                     int32_t num_iterations, int32_t thinning, int32_t burn_in, uint64_t seed) {
   if (interval < 0 || Dh < 0 || num_iterations < 0 || burn_in < 0 || thinning < 1)
@@ -2082,6 +2106,21 @@ lda_status ldatm_evaluate(ldatm* m, int64_t Dh, const int64_t* doc_off, const in
   return guard([&] {
     const double t = m->model.evaluate(Dh, doc_off, words, num_iterations, thinning, burn_in, seed, doc_ll,
                                        tokens_scored, theta_out);
+    if (total) *total = t;
+  });
+}
+
+lda_status ldatm_left_to_right(ldatm* m, int64_t Dh, const int64_t* doc_off, const int32_t* words,
+                               int32_t num_particles, int32_t resampling, uint64_t seed, double* doc_ll,
+                               double* total, int64_t* tokens_scored) {
+  TM_CHECK(m);
+  if (Dh > 0 && !doc_ll) {
+    g_tm_error = "null doc_ll";
+    return LDA_ERR_INVALID_ARG;
+  }
+  return guard([&] {
+    const double t = m->model.leftToRight(Dh, doc_off, words, num_particles, resampling, seed, doc_ll,
+                                          tokens_scored);
     if (total) *total = t;
   });
 }

@@ -171,6 +171,11 @@ class ParallelTopicModel {
   static void completionSplit(int32_t V, int64_t Dh, const int64_t* doc_off, const int32_t* words,
                               std::vector<int64_t>& obs_off, std::vector<int32_t>& obs,
                               std::vector<int64_t>& sc_off, std::vector<int32_t>& sc);
+  // Mallet's MarginalProbEstimator.evaluateLeftToRight (lda_left_to_right on
+  // shard 0, for the same reason): tokens outside [0, V) are dropped and not
+  // counted; doc_ll[Dh]; tokens_scored may be null; returns the total
+  double leftToRight(int64_t Dh, const int64_t* doc_off, const int32_t* words, int32_t num_particles,
+                     int32_t resampling, uint64_t seed, double* doc_ll, int64_t* tokens_scored);
   // a held-out set evaluated by estimate() after every interval-th sweep
   // (interval 0: off); not part of the checkpoint
   void setHeldOut(int64_t Dh, const int64_t* doc_off, const int32_t* words, int32_t interval,

@@ -508,6 +508,35 @@ class GibbsSampler:
             theta.ctypes.data if return_theta else None), "lda_doc_completion")
         return (doc_ll, total.value, theta) if return_theta else (doc_ll, total.value)
 
+    def left_to_right(self, doc_off, words, particles: int = 10, resampling: bool = True, seed: int = 0,
+                      token_prob: bool = False, z: bool = False):
+        """lda_left_to_right: Mallet's MarginalProbEstimator.evaluateLeftToRight
+        (Wallach et al.'s left-to-right particle estimator of log p(w | model))
+        of Dh held-out documents (doc_off[Dh + 1], words, ids in [0, V)) against
+        the model's current counts, on the device.  Returns (doc_ll[Dh], total,
+        tokens_scored), then with token_prob the per-token estimate phat[N] (0
+        for a skipped token) and with z each particle's final topics
+        [particles, N] (-1 for a skipped token)."""
+        off, w = capi.as_docs(doc_off, words)
+        particles = int(particles)
+        if particles < 1:
+            raise ValueError("particles must be at least 1")
+        Dh, N = len(off) - 1, len(w)
+        doc_ll = np.zeros(Dh, dtype=np.float64)
+        total, tokens = C.c_double(0.0), C.c_int64(0)
+        tp = np.zeros(N, dtype=np.float64) if token_prob else None
+        zo = np.full((particles, N), -1, dtype=np.int32) if z else None
+        capi.check(self._L.lda_left_to_right(
+            self._h, Dh, off.ctypes.data, w.ctypes.data if N else None, particles, 1 if resampling else 0,
+            int(seed) & (2**64 - 1), doc_ll.ctypes.data, C.addressof(total), C.addressof(tokens),
+            tp.ctypes.data if token_prob else None, zo.ctypes.data if z else None), "lda_left_to_right")
+        out = (doc_ll, total.value, tokens.value)
+        if token_prob:
+            out += (tp,)
+        if z:
+            out += (zo,)
+        return out
+
     # ------------------------------------------- hyperparameter statistics
     def max_doc_length(self) -> int:
         m = C.c_int32()

@@ -94,6 +94,7 @@ TM_SIGNATURES = {
     "ldatm_score_top": (_i32, [_vp, _i32, C.c_int64, _vp, _i32, _vp, _vp]),
     "ldatm_heldout_loglik": (_i32, [_vp, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
     "ldatm_evaluate": (_i32, [_vp, C.c_int64, _vp, _vp, _i32, _i32, _i32, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "ldatm_left_to_right": (_i32, [_vp, C.c_int64, _vp, _vp, _i32, _i32, C.c_uint64, _vp, _vp, _vp]),
     "ldatm_completion_split": (_i32, [_i32, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ldatm_set_held_out": (_i32, [_vp, C.c_int64, _vp, _vp, _i32, _i32, _i32, _i32, C.c_uint64]),
     "ldatm_get_held_out_trace": (_i32, [_vp, _vp, _vp, _i32, C.POINTER(_i32)]),
@@ -589,6 +590,9 @@ class ParallelTopicModel:
     def getHeldOutEvaluator(self) -> "HeldOutEvaluator":
         return HeldOutEvaluator(self)
 
+    def getProbEstimator(self) -> "MarginalProbEstimator":
+        return MarginalProbEstimator(self)
+
     def heldOutLogLikelihood(self, theta, doc_off, words):
         """ldatm_heldout_loglik: (doc_ll[Dh], total) of the scored tokens
         (doc_off[Dh + 1], words, ids in [0, V)) under theta[Dh, K] and the
@@ -734,6 +738,61 @@ class HeldOutEvaluator:
                                             int(seed) & (2**64 - 1), doc_ll.ctypes.data, C.addressof(total),
                                             C.addressof(tokens), theta.ctypes.data), "evaluate")
         return HeldOutResult(total.value, tokens.value, doc_ll, theta)
+
+
+class LeftToRightResult:
+    """What MarginalProbEstimator.leftToRight returns."""
+
+    def __init__(self, logLikelihood: float, tokens: int, perDocument):
+        self.logLikelihood = float(logLikelihood)
+        self.tokens = int(tokens)
+        self.perDocument = perDocument
+
+    @property
+    def perplexity(self) -> float:
+        return float(np.exp(-self.logLikelihood / self.tokens)) if self.tokens else float("nan")
+
+    def __repr__(self):
+        return (f"LeftToRightResult(logLikelihood={self.logLikelihood!r}, tokens={self.tokens}, "
+                f"perplexity={self.perplexity!r})")
+
+
+class MarginalProbEstimator:
+    """Mallet's MarginalProbEstimator (ParallelTopicModel.getProbEstimator()):
+    the left-to-right particle estimator of log p(w | model) of held-out
+    documents against the model's current counts, on the device
+    (ldatm_left_to_right)."""
+
+    def __init__(self, model: ParallelTopicModel):
+        self.model = model
+
+    def leftToRight(self, instances, numParticles: int = 10, usingResampling: bool = True,
+                    seed: int = 0) -> LeftToRightResult:
+        """Ids outside the model's vocabulary are dropped and not counted; a
+        token whose type has no training tokens is skipped."""
+        numParticles = int(numParticles)
+        if numParticles < 1:
+            raise ValueError("numParticles must be at least 1")
+        off, w = _flatten(list(instances))
+        Dh = len(off) - 1
+        doc_ll = np.zeros(Dh, np.float64)
+        total, tokens = C.c_double(0.0), C.c_int64(0)
+        _check(self.model._L.ldatm_left_to_right(self.model._h, Dh, off.ctypes.data, w.ctypes.data if len(w) else None,
+                                                 numParticles, 1 if usingResampling else 0, int(seed) & (2**64 - 1),
+                                                 doc_ll.ctypes.data, C.addressof(total), C.addressof(tokens)),
+               "evaluateLeftToRight")
+        return LeftToRightResult(total.value, tokens.value, doc_ll)
+
+    def evaluateLeftToRight(self, instances, numParticles: int, usingResampling: bool,
+                            docProbabilityStream=None) -> float:
+        """Mallet's signature: the total log likelihood; each document's log
+        likelihood goes to docProbabilityStream, one line per document (Java's
+        Double.toString, as println writes it)."""
+        r = self.leftToRight(instances, numParticles, usingResampling)
+        if docProbabilityStream is not None:
+            for x in r.perDocument:
+                docProbabilityStream.write(format_double(float(x)) + "\n")
+        return r.logLikelihood
 
 
 def _doc_ids(docs, model):
