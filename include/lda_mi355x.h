@@ -609,6 +609,74 @@ lda_status lda_topic_word_stats(lda_ctx* ctx, int32_t n, const int32_t* word_ids
                                 int32_t* counts /*[K*n]*/, int64_t* totals /*[K*n]*/,
                                 double* share_sums /*[K*n]*/, uint64_t* sumsq /*[K]*/);
 
+/* Topic distances and nearest topics, within one model or between two, on the
+ * device from the global int32 nw rows and nwsum.  other ==
+ * NULL or other == ctx is SELF mode (K2 = K); else CROSS mode: topic a of ctx
+ * against topic b of other, which must hold the same V (word ids must mean the
+ * same words: aligning vocabularies is the caller's job) on the same device.
+ * Each side's smoothed topic uses its own beta and nwsum,
+ *     phi_k(w) = (nw[w,k] + beta) / (nwsum[k] + V beta),   V beta = (double) V * beta,
+ * an IEEE fp64 division.  With p = phi_a of ctx and q = phi_b of other, sums
+ * over the words w, natural logarithms, everything in fp64:
+ *  LDA_TOPIC_COSINE     sum p q / sqrt(sum p^2 * sum q^2)       (a similarity)
+ *  LDA_TOPIC_HELLINGER  sqrt(min(1, (1/2) sum (sqrt p - sqrt q)^2))
+ *                       = sqrt(1 - sum sqrt p sqrt q), in [0, 1]
+ *  LDA_TOPIC_JS         max(0, (1/2) [sum p ln p + sum q ln q
+ *                                     - sum (p + q) ln((p + q) / 2)]),
+ *                       Jensen-Shannon in nats, in [0, ln 2]
+ *  LDA_TOPIC_KL         sum p ln p - sum p ln q = KL(p || q); row = p
+ * (the Hellinger and Jensen-Shannon forms are chosen so that equal columns
+ * give exactly 0, below).  out[a * K2 + b], a < K, b < K2; padded topics are
+ * never reported.
+ * Determinism.  The word rows are cut into slabs that are a function of
+ * (V, K, K2) alone -- lda_topic_distance_slabs; never of the device: s =
+ * max(1, min(ceil(V / 256), floor(LDA_TOPIC_SCRATCH_CAP_MIB MiB / (8 K K2)),
+ * 64)), slab_rows = ceil(V / s), slabs = ceil(V / slab_rows).  Every sum (the
+ * pair sums and the per-topic sums alike) adds a slab's rows in ascending
+ * order from 0.0 and then the slabs in slab order; no floating-point atomics.
+ * So a pair's value is a function of the two columns, the two (beta, nwsum)
+ * and V alone, not of where the pair sits in the matrix: two topics with
+ * identical columns (and equal nwsum) have bit-identical distances to every
+ * third topic and distance exactly 0 (cosine exactly 1) to each other, and a
+ * call repeats bit for bit.
+ * Self mode: cosine, Hellinger and Jensen-Shannon are bit-symmetric by
+ * construction (only pairs a < b are computed; (b, a) is a copy) and the
+ * diagonal is set, not computed: 1 for cosine, 0 for the others, also for
+ * Kullback-Leibler, whose other cells are as computed.
+ * Cross mode: the kernels run on ctx's stream and read other's nw / nwsum
+ * after waiting for other's stream; nothing of other is written.
+ * Errors, checked in this order before any device work: LDA_ERR_INVALID_ARG
+ * for a NULL ctx, a metric outside [0, 3], (nearest) n outside
+ * [1, LDA_TOPIC_NEAREST_MAX], a NULL output, V differing between the two
+ * contexts; LDA_ERR_UNSUPPORTED for contexts on different devices;
+ * LDA_ERR_STATE with a pending delta on either side (call lda_apply first) or
+ * V = 0.
+ * Cost: V K K2 terms (half in self mode for the symmetric metrics), dense on
+ * purpose.  Device scratch is grow-only and kept by ctx: the slabs' pair sums,
+ * at most LDA_TOPIC_SCRATCH_CAP_MIB MiB (one 8 K K2-byte plane if that is
+ * more: 128 MiB at K = K2 = 4096), the matrix (8 K K2 bytes) and the per-topic
+ * sums (at most 65 x 16 (Kp + Kp2) bytes).  Waits for ctx's stream.
+ *
+ * lda_topic_nearest: the same matrix, kept on the device, and per row a the n
+ * nearest topics b of the other side: value ascending (cosine: descending),
+ * equal values by ascending topic id (-0.0 counts as 0.0); topics[a * n + i],
+ * values[a * n + i] (the matrix's own bits).  In self mode topic a is not a
+ * candidate of its own row.  With fewer than n candidates the tail holds id
+ * -1 and value NaN.  Only the K n ids and values are copied to the host. */
+#define LDA_TOPIC_COSINE 0
+#define LDA_TOPIC_HELLINGER 1
+#define LDA_TOPIC_JS 2
+#define LDA_TOPIC_KL 3
+#define LDA_TOPIC_NEAREST_MAX 64
+#define LDA_TOPIC_SCRATCH_CAP_MIB 256
+lda_status lda_topic_distances(lda_ctx* ctx, lda_ctx* other /* NULL = ctx itself */, int32_t metric,
+                               double* out /* [K * K2], row a = topic a of ctx */);
+lda_status lda_topic_nearest(lda_ctx* ctx, lda_ctx* other /* NULL = ctx itself */, int32_t metric, int32_t n,
+                             int32_t* topics /* [K * n] */, double* values /* [K * n] */);
+/* Host-only: the slabs lda_topic_distances cuts V word rows into for a K x K2
+ * matrix (slab s holds rows [s * slab_rows, min(V, (s + 1) * slab_rows))). */
+lda_status lda_topic_distance_slabs(int32_t V, int32_t K, int32_t K2, int32_t* slabs, int32_t* slab_rows);
+
 /* Mallet-layout adapter: typeTopicCounts as packed (count << topic_bits) |
  * topic rows sorted descending, rows[row_off[w] .. row_off[w+1]) with
  * row_off[V+1]; row length = min(K, typeTotal[w]) exactly as Mallet allocates
@@ -717,7 +785,8 @@ void lda_debug_fail_host_alloc(int32_t nth);
  * lda_heldout_loglik and lda_doc_completion, then lda_top_words,
  * lda_doc_top_topics and lda_doc_counts, then lda_topic_codocuments and
  * lda_topic_word_stats, then lda_left_to_right (with its test hook
- * lda_debug_ltr_chunk_cells) came later and only add symbols, so the
+ * lda_debug_ltr_chunk_cells), then lda_topic_distances, lda_topic_nearest
+ * and lda_topic_distance_slabs came later and only add symbols, so the
  * version stays 8. */
 #define LDA_ABI_VERSION 8
 const char* lda_version(void);

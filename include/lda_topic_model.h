@@ -182,6 +182,30 @@ lda_status ldatm_doc_top_topics(ldatm* m, int32_t mtop, int64_t M, const int64_t
                                 int32_t* topics /*[M*mtop]*/, int32_t* counts /*[M*mtop]*/);
 lda_status ldatm_doc_counts(ldatm* m, int64_t M, const int64_t* docs, int32_t* nd /*[M*K]*/);
 
+/* Topic distances and nearest topics within one model or between two
+ * (lda_topic_distances / lda_topic_nearest of lda_mi355x.h; the
+ * metrics are LDA_TOPIC_COSINE, _HELLINGER, _JS, _KL as defined there).
+ * other == NULL or other == m: the model against itself (K2 = K); else topic a
+ * of m against topic b of other, each side with its own beta.  The two
+ * models must hold the same num_types, and word ids must mean the same words
+ * in both: aligning vocabularies is the caller's job.  Both calls run on
+ * shard 0 of each model -- every shard holds the same global counts, so the
+ * result does not depend on the number of shards, bit for bit.
+ * ldatm_topic_distances: out[K*K2], row a = topic a of m.
+ * ldatm_nearest_topics: per topic a of m the n nearest topics of other,
+ * value ascending (cosine: descending), ties by ascending topic id, the topic
+ * itself left out when the model is compared with itself; topics[K*n],
+ * values[K*n]; id -1 and NaN past the last candidate.
+ * Errors, checked in this order before any device work (a model without a
+ * GPU names its bad argument, not the missing device): LDA_ERR_INVALID_ARG for
+ * a NULL model, a metric outside [0, 3], n outside [1, LDA_TOPIC_NEAREST_MAX],
+ * a NULL output, num_types differing.  When shard 0 of the two models sit on
+ * different devices, lda_topic_distances' LDA_ERR_UNSUPPORTED is passed on
+ * with its message.  Waits for shard 0's streams. */
+lda_status ldatm_topic_distances(ldatm* m, ldatm* other /* NULL = m */, int32_t metric, double* out /*[K*K2]*/);
+lda_status ldatm_nearest_topics(ldatm* m, ldatm* other /* NULL = m */, int32_t metric, int32_t n,
+                                int32_t* topics /*[K*n]*/, double* values /*[K*n]*/);
+
 /* Topic diagnostics: per topic the figures Mallet's
  * TopicModelDiagnostics reports (train-topics --diagnostics-file), from
  * integer statistics counted on the device (lda_topic_codocuments,

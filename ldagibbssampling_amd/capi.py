@@ -40,6 +40,28 @@ DIAG_PROPS_MAX = 8
 # LDA_LTR_MAX_PARTICLES / LDA_LTR_MAX_DOC_TOKENS of lda_mi355x.h
 LTR_MAX_PARTICLES = 1024
 LTR_MAX_DOC_TOKENS = 4096
+# LDA_TOPIC_* metrics and LDA_TOPIC_NEAREST_MAX of lda_mi355x.h
+TOPIC_METRICS = {"cosine": 0, "hellinger": 1, "jensen_shannon": 2, "kullback_leibler": 3}
+TOPIC_NEAREST_MAX = 64
+
+
+def topic_metric(metric) -> int:
+    """LDA_TOPIC_* of a metric name or integer; an unknown one is refused
+    before any native call."""
+    if isinstance(metric, str):
+        if metric not in TOPIC_METRICS:
+            raise ValueError(f"metric must be one of {sorted(TOPIC_METRICS)}, not {metric!r}")
+        return TOPIC_METRICS[metric]
+    if isinstance(metric, (bool, float)) or int(metric) not in TOPIC_METRICS.values():
+        raise ValueError(f"metric must be one of {sorted(TOPIC_METRICS)} or 0..3, not {metric!r}")
+    return int(metric)
+
+
+def topic_nearest_n(n) -> int:
+    n = int(n)
+    if not 1 <= n <= TOPIC_NEAREST_MAX:
+        raise ValueError(f"n must be in [1, {TOPIC_NEAREST_MAX}]")
+    return n
 
 
 def score_metric(metric) -> int:
@@ -153,6 +175,10 @@ SIGNATURES = {
     "lda_doc_counts": (C.c_int32, [_vp, C.c_int64, C.c_int64, _vp, _vp]),
     "lda_topic_codocuments": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
     "lda_topic_word_stats": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "lda_topic_distances": (C.c_int32, [_vp, _vp, C.c_int32, _vp]),
+    "lda_topic_nearest": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
+    "lda_topic_distance_slabs": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_int32)]),
     "lda_to_mallet_packed": (C.c_int32, [_vp, _vp, _i64p, C.POINTER(C.c_int32)]),
     "lda_max_doc_length": (C.c_int32, [_vp, C.POINTER(C.c_int32)]),
     "lda_doc_topic_histograms": (C.c_int32, [_vp, C.c_int32, _i32p, _i32p]),

@@ -248,6 +248,13 @@ constexpr int64_t READOUT_DOCS = int64_t(1) << 20;
 // cells to the result once
 constexpr int CODOC_WAVES = 16;
 constexpr int64_t CODOC_BLOCKS_PER_CU = 2;
+// lda_topic_distances' slabs of word rows: at least TOPIC_SLAB_ROWS rows
+// each, at most lda::TOPIC_MAX_SLABS of them, and as many as keep the slabs'
+// pair sums (8 K K2 bytes per slab) within TOPIC_PART_BYTES -- one slab when a
+// single plane is larger.  A function of (V, K, K2) alone.
+constexpr int64_t TOPIC_SLAB_ROWS = 256;
+constexpr int64_t TOPIC_PART_BYTES = int64_t(256) << 20;
+static_assert(TOPIC_PART_BYTES == LDA_TOPIC_SCRATCH_CAP_MIB * (int64_t(1) << 20), "the header states the cap");
 
 }  // namespace
 
@@ -340,7 +347,12 @@ struct lda_ctx {
   unsigned long long* ro_lists = nullptr;
   int32_t* ro_out = nullptr;
   int64_t* ro_docs = nullptr;
-  size_t ro_cap[3] = {};
+  // lda_topic_distances / lda_topic_nearest (slots 3..7): the slabs' pair
+  // sums [slabs x K x K2], the per-topic sums of both sides (slabs and
+  // totals), the matrix [K x K2], the nearest ids and values [K x n]
+  double *ro_part = nullptr, *ro_sums = nullptr, *ro_mat = nullptr, *ro_vals = nullptr;
+  int32_t* ro_ids = nullptr;
+  size_t ro_cap[8] = {};
   // lda_topic_codocuments / lda_topic_word_stats: grow-only scratch -- the
   // word lists [K n], the (word, topic) -> slot table, the integer results
   // and lda_topic_word_stats' fp64 sums
@@ -498,6 +510,7 @@ struct lda_ctx {
                     (void*)held_theta, (void*)held_ll, (void*)held_inv, (void*)held_words, (void*)held_off,
                     (void*)ltr_z, (void*)ltr_words, (void*)ltr_p, (void*)ltr_phat, (void*)ltr_ll, (void*)ltr_off,
                     (void*)ro_lists, (void*)ro_out, (void*)ro_docs,
+                    (void*)ro_part, (void*)ro_sums, (void*)ro_mat, (void*)ro_vals, (void*)ro_ids,
                     (void*)dg_ids, (void*)dg_table, (void*)dg_out, (void*)dg_shares,
                     (void*)perm, (void*)items, (void*)warm.range_doc, (void*)steady.range_doc,
                     (void*)big.tab, (void*)big.tab_m1, (void*)big.F, (void*)big.pfx, (void*)big.scal})
@@ -2747,6 +2760,144 @@ lda_status lda_topic_word_stats(lda_ctx* c, int32_t n, const int32_t* word_ids, 
   HIP_TRY(hipMemcpyAsync(totals, a.totals, sizeof(int64_t) * cells, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(share_sums, a.share_sums, sizeof(double) * cells, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(sumsq, a.sumsq, sizeof(uint64_t) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LDA_OK;
+  });
+}
+
+namespace {
+
+// lda_topic_distances' slabs (TOPIC_SLAB_ROWS, TOPIC_PART_BYTES above)
+void topic_slabs(int64_t V, int64_t K, int64_t K2, int64_t* slabs, int64_t* slab_rows) {
+  const int64_t by_rows = (V + TOPIC_SLAB_ROWS - 1) / TOPIC_SLAB_ROWS;
+  const int64_t by_bytes = TOPIC_PART_BYTES / (8 * K * K2);
+  int64_t s = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(by_rows, by_bytes), lda::TOPIC_MAX_SLABS));
+  const int64_t rows = std::max<int64_t>(1, (V + s - 1) / s);
+  s = std::max<int64_t>(1, (V + rows - 1) / rows);
+  *slabs = s;
+  *slab_rows = rows;
+}
+
+// the arguments of lda_topic_distances / lda_topic_nearest, in the order the
+// header lists them; n == nullptr: no n.  o becomes the other side (c itself
+// in self mode).
+lda_status check_topic_pair(lda_ctx* c, lda_ctx*& o, int32_t metric, const int32_t* n, bool outputs) {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (metric < LDA_TOPIC_COSINE || metric > LDA_TOPIC_KL)
+    return fail(LDA_ERR_INVALID_ARG, "metric must be LDA_TOPIC_COSINE, _HELLINGER, _JS or _KL");
+  if (n && (*n < 1 || *n > LDA_TOPIC_NEAREST_MAX))
+    return fail(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_TOPIC_NEAREST_MAX]");
+  if (!outputs) return fail(LDA_ERR_INVALID_ARG, "null output");
+  if (!o) o = c;
+  if (o->V != c->V) return fail(LDA_ERR_INVALID_ARG, "the two contexts differ in num_types (V)");
+  if (o->device != c->device) return fail(LDA_ERR_UNSUPPORTED, "the two contexts are on different devices");
+  if (c->pending || o->pending)
+    return fail(LDA_ERR_STATE, "topic distances with a pending delta: call lda_apply first");
+  if (c->V == 0) return fail(LDA_ERR_STATE, "topic distances of an empty vocabulary (V = 0)");
+  return LDA_OK;
+}
+
+// the K x K2 matrix of lda_topic_distances into c->ro_mat, on c's stream
+lda_status topic_matrix(lda_ctx* c, lda_ctx* o, int32_t metric) {
+  const bool self = o == c;
+  const int64_t K = c->K, K2 = o->K;
+  int64_t slabs, slab_rows;
+  topic_slabs(c->V, K, K2, &slabs, &slab_rows);
+  HIP_TRY(hipSetDevice(c->device));
+  // the other context's counts must be final before this stream reads them
+  if (!self) HIP_TRY(hipStreamSynchronize(o->stream));
+  const size_t sums_a = (size_t)(slabs + 1) * 2 * (size_t)c->Kp, sums_b = self ? 0 : (size_t)(slabs + 1) * 2 * (size_t)o->Kp;
+  HIP_TRY(ro_need(c, c->ro_part, (size_t)(slabs * K * K2), 3));
+  HIP_TRY(ro_need(c, c->ro_sums, sums_a + sums_b, 4));
+  HIP_TRY(ro_need(c, c->ro_mat, (size_t)(K * K2), 5));
+  auto sums = [&](const lda_ctx* x, double* at) -> hipError_t {
+    lda::TopicSumsArgs s{};
+    s.nw = x->nw;
+    s.nwsum = x->nwsum;
+    s.V = x->V;
+    s.Kp = x->Kp;
+    s.beta = x->beta;
+    s.vbeta = (double)x->V * x->beta;
+    s.slabs = (int32_t)slabs;
+    s.slab_rows = (int32_t)slab_rows;
+    s.sums = at;
+    s.tot = at + (size_t)slabs * 2 * (size_t)x->Kp;
+    return lda::launch_topic_sums(s, c->stream);
+  };
+  HIP_TRY(sums(c, c->ro_sums));
+  if (!self) HIP_TRY(sums(o, c->ro_sums + sums_a));
+  lda::TopicPairArgs a{};
+  a.nw_a = c->nw;
+  a.nwsum_a = c->nwsum;
+  a.nw_b = o->nw;
+  a.nwsum_b = o->nwsum;
+  a.V = c->V;
+  a.K = c->K;
+  a.Kp = c->Kp;
+  a.K2 = o->K;
+  a.Kp2 = o->Kp;
+  a.metric = metric;
+  a.beta_a = c->beta;
+  a.vbeta_a = (double)c->V * c->beta;
+  a.beta_b = o->beta;
+  a.vbeta_b = (double)o->V * o->beta;
+  a.slabs = (int32_t)slabs;
+  a.slab_rows = (int32_t)slab_rows;
+  a.self = self;
+  a.upper = self && metric != LDA_TOPIC_KL;
+  a.part = c->ro_part;
+  a.tot_a = c->ro_sums + (size_t)slabs * 2 * (size_t)c->Kp;
+  a.tot_b = self ? a.tot_a : c->ro_sums + sums_a + (size_t)slabs * 2 * (size_t)o->Kp;
+  a.out = c->ro_mat;
+  HIP_TRY(lda::launch_topic_pairs(a, c->stream));
+  HIP_TRY(lda::launch_topic_dist_final(a, c->stream));
+  return LDA_OK;
+}
+
+}  // namespace
+
+lda_status lda_topic_distance_slabs(int32_t V, int32_t K, int32_t K2, int32_t* slabs, int32_t* slab_rows) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (V < 1 || K < 1 || K2 < 1 || K > LDA_MAX_TOPICS || K2 > LDA_MAX_TOPICS)
+    return fail(LDA_ERR_INVALID_ARG, "bad sizes");
+  int64_t s, r;
+  topic_slabs(V, K, K2, &s, &r);
+  if (slabs) *slabs = (int32_t)s;
+  if (slab_rows) *slab_rows = (int32_t)r;
+  return LDA_OK;
+  });
+}
+
+lda_status lda_topic_distances(lda_ctx* c, lda_ctx* o, int32_t metric, double* out) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (lda_status s = check_topic_pair(c, o, metric, nullptr, out != nullptr); s != LDA_OK) return s;
+  if (lda_status s = topic_matrix(c, o, metric); s != LDA_OK) return s;
+  HIP_TRY(hipMemcpyAsync(out, c->ro_mat, sizeof(double) * (size_t)c->K * (size_t)o->K, hipMemcpyDeviceToHost,
+                         c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LDA_OK;
+  });
+}
+
+lda_status lda_topic_nearest(lda_ctx* c, lda_ctx* o, int32_t metric, int32_t n, int32_t* topics, double* values) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (lda_status s = check_topic_pair(c, o, metric, &n, topics && values); s != LDA_OK) return s;
+  if (lda_status s = topic_matrix(c, o, metric); s != LDA_OK) return s;
+  const size_t cells = (size_t)c->K * (size_t)n;
+  HIP_TRY(ro_need(c, c->ro_ids, cells, 6));
+  HIP_TRY(ro_need(c, c->ro_vals, cells, 7));
+  lda::TopicNearestArgs a{};
+  a.mat = c->ro_mat;
+  a.K = c->K;
+  a.K2 = o->K;
+  a.n = n;
+  a.self = o == c;
+  a.descending = metric == LDA_TOPIC_COSINE;
+  a.topics = c->ro_ids;
+  a.values = c->ro_vals;
+  HIP_TRY(lda::launch_topic_nearest(a, c->stream));
+  HIP_TRY(hipMemcpyAsync(topics, a.topics, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(values, a.values, sizeof(double) * cells, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return LDA_OK;
   });

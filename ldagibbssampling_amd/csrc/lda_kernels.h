@@ -375,6 +375,69 @@ struct LeftToRightArgs {
 };
 hipError_t launch_left_to_right(const LeftToRightArgs& a, hipStream_t st);
 hipError_t launch_ltr_reduce(const LeftToRightArgs& a, hipStream_t st);
+// lda_topic_distances / lda_topic_nearest.  Side A is the
+// calling context (topic a = row of the result), side B the other one (the
+// same arrays in self mode).  phi = (nw + beta) / (nwsum + vbeta), an IEEE
+// division, in every kernel that forms it.  The rows are cut into `slabs`
+// slabs of slab_rows rows, the same cut for the per-topic sums and the pairs;
+// within a slab every sum adds its rows in ascending order from 0.0, and the
+// slabs are added in slab order, so a sum over the same values is the same
+// bits wherever it is computed.
+//  k_topic_sums          grid (slabs, Kp / 64), lane per topic: the slab's
+//                        sum of phi^2 and of phi ln phi,
+//                        sums[(slab * 2 + which) * Kp + k]
+//  k_topic_sums_reduce   tot[which * Kp + k] = the slabs added in order
+//  k_topic_pairs<metric> grid (b tiles, a tiles, slabs), 256 threads: a 64 x
+//                        64 tile of pairs over one slab, TOPIC_PAIR_ROWS rows
+//                        at a time through LDS, a 4 x 4 fp64 register tile
+//                        per thread (a = ty + 16 i, b = tx + 16 j); the
+//                        slab's sums go to part[(slab * K + a) * K2 + b].
+//                        With `upper` set (self mode, symmetric metric) the
+//                        tiles below the diagonal are not computed.
+//  k_topic_dist_final    one thread per cell: adds the slabs in order and
+//                        closes the metric; with `upper` the cell (a, b),
+//                        a > b, is computed from the sums of (b, a), and in
+//                        self mode the diagonal is set (1 for cosine, else 0)
+//  k_topic_nearest       one wave per row of the matrix: n rounds of a
+//                        wave-wide minimum over (order key, topic id)
+// The term summed over the words and the closing expression per metric:
+//  cosine     p q                 S / sqrt(sum p^2 * sum q^2)
+//  Hellinger  (sqrt p - sqrt q)^2 sqrt(min(1, S / 2))
+//  JS         (p + q) ln((p+q)/2) max(0, (sum p ln p + sum q ln q - S) / 2)
+//  KL         p ln q              sum p ln p - S
+constexpr int TOPIC_COSINE = 0, TOPIC_HELLINGER = 1, TOPIC_JS = 2, TOPIC_KL = 3;
+constexpr int TOPIC_PAIR_ROWS = 32;
+constexpr int TOPIC_MAX_SLABS = 64;
+struct TopicSumsArgs {
+  const int32_t* nw;        // [V * Kp]
+  const int32_t* nwsum;     // [Kp]
+  int32_t V, Kp;
+  double beta, vbeta;
+  int32_t slabs, slab_rows;
+  double* sums;             // [slabs * 2 * Kp]
+  double* tot;              // [2 * Kp]
+};
+hipError_t launch_topic_sums(const TopicSumsArgs& a, hipStream_t st);
+struct TopicPairArgs {
+  const int32_t *nw_a, *nwsum_a, *nw_b, *nwsum_b;
+  int32_t V, K, Kp, K2, Kp2, metric;
+  double beta_a, vbeta_a, beta_b, vbeta_b;
+  int32_t slabs, slab_rows;
+  int32_t self, upper;      // self mode; only the tiles on and above the diagonal
+  double* part;             // [slabs * K * K2]
+  const double* tot_a;      // [2 * Kp]
+  const double* tot_b;      // [2 * Kp2]
+  double* out;              // [K * K2]
+};
+hipError_t launch_topic_pairs(const TopicPairArgs& a, hipStream_t st);
+hipError_t launch_topic_dist_final(const TopicPairArgs& a, hipStream_t st);
+struct TopicNearestArgs {
+  const double* mat;        // [K * K2]
+  int32_t K, K2, n, self, descending;
+  int32_t* topics;          // [K * n]
+  double* values;           // [K * n]
+};
+hipError_t launch_topic_nearest(const TopicNearestArgs& a, hipStream_t st);
 // range workers per block of the sampler kernel used for (C, sampler): 4
 // waves, 16 for the large-K sparse kernel (C >= 32), 8 for the half-wave
 // dense kernel (4 waves x 2 halves)

@@ -3567,6 +3567,214 @@ __global__ __launch_bounds__(64) void k_sumsq(const WordStatsArgs a) {
   if (k < a.K && acc) atomicAdd(&a.sumsq[k], acc);
 }
 
+// ---- lda_topic_distances / lda_topic_nearest (lda_kernels.h)
+
+// The per-topic sums of a slab: lane l on column group * 64 + l (a row's
+// segment is one coalesced 256-byte load), eight rows in flight, the rows
+// added in ascending order.  p and p ln p are formed exactly as k_topic_pairs
+// forms them, so that a topic's sums equal its pair sums with an identical
+// column bit for bit.
+__global__ __launch_bounds__(64) void k_topic_sums(const TopicSumsArgs a) {
+  const int lane = threadIdx.x, s = blockIdx.x, k = (int)blockIdx.y * 64 + lane;
+  const int32_t* __restrict__ col = a.nw + k;
+  const double denom = (double)a.nwsum[k] + a.vbeta;
+  const int64_t w0 = (int64_t)s * a.slab_rows, w1 = min((int64_t)a.V, w0 + a.slab_rows);
+  double s2 = 0.0, sl = 0.0;
+  for (int64_t w = w0; w < w1; w += 8) {
+    int32_t c[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) c[u] = w + u < w1 ? col[(size_t)(w + u) * a.Kp] : 0;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      if (w + u < w1) {
+        const double p = ((double)c[u] + a.beta) / denom;
+        s2 += p * p;
+        sl += p * log(p);
+      }
+    }
+  }
+  a.sums[((size_t)s * 2 + 0) * a.Kp + k] = s2;
+  a.sums[((size_t)s * 2 + 1) * a.Kp + k] = sl;
+}
+
+__global__ __launch_bounds__(256) void k_topic_sums_reduce(const TopicSumsArgs a) {
+  const int i = (int)(blockIdx.x * 256 + threadIdx.x);   // which * Kp + k
+  if (i >= 2 * a.Kp) return;
+  double t = 0.0;
+  for (int s = 0; s < a.slabs; ++s) t += a.sums[(size_t)s * 2 * a.Kp + i];
+  a.tot[i] = t;
+}
+
+// what a side keeps in LDS per (row, topic) and the term of a pair
+template <int METRIC, bool B>
+__device__ __forceinline__ double topic_stage(double p) {
+  if constexpr (METRIC == TOPIC_HELLINGER) return sqrt(p);
+  if constexpr (METRIC == TOPIC_KL && B) return log(p);
+  return p;
+}
+template <int METRIC>
+__device__ __forceinline__ double topic_term(double x, double y) {
+  if constexpr (METRIC == TOPIC_HELLINGER) {
+    const double d = x - y;
+    return d * d;
+  } else if constexpr (METRIC == TOPIC_JS) {
+    const double s = x + y;
+    return s * log(0.5 * s);
+  } else {
+    return x * y;
+  }
+}
+
+// One 64 x 64 tile of pairs over one slab of rows.  Thread t loads column
+// t & 63 of rows (t >> 6) + 4 u of each side's segment (coalesced 256-byte
+// rows), transforms the count once on the way into LDS, and accumulates the
+// pairs a = ty + 16 i, b = tx + 16 j (tx = t & 15, ty = t >> 4) in a 4 x 4 fp64
+// register tile: per row 4 + 4 LDS reads of 8 bytes -- the a values a
+// broadcast within each 16 lanes, the b values consecutive -- for 16 terms.
+// The next chunk's counts are loaded into registers while this one is summed.
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_topic_pairs(const TopicPairArgs a) {
+  __shared__ double As[TOPIC_PAIR_ROWS][64], Bs[TOPIC_PAIR_ROWS][64];
+  const int tb = blockIdx.x, ta = blockIdx.y, s = blockIdx.z;
+  if (a.upper && ta > tb) return;
+  constexpr int PER = TOPIC_PAIR_ROWS / 4;
+  const int tid = threadIdx.x, col = tid & 63, r0 = tid >> 6, tx = tid & 15, ty = tid >> 4;
+  const int ka = ta * 64 + col, kb = tb * 64 + col;   // < Kp, < Kp2
+  const double da = (double)a.nwsum_a[ka] + a.vbeta_a, db = (double)a.nwsum_b[kb] + a.vbeta_b;
+  const int32_t* __restrict__ ca = a.nw_a + ka;
+  const int32_t* __restrict__ cb = a.nw_b + kb;
+  const int64_t w0 = (int64_t)s * a.slab_rows, w1 = min((int64_t)a.V, w0 + a.slab_rows);
+  int32_t na[PER], nb[PER];
+  auto fetch = [&](int64_t w) {
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int64_t row = w + r0 + 4 * u;
+      na[u] = row < w1 ? ca[(size_t)row * a.Kp] : 0;
+      nb[u] = row < w1 ? cb[(size_t)row * a.Kp2] : 0;
+    }
+  };
+  double acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
+  fetch(w0);
+  for (int64_t w = w0; w < w1; w += TOPIC_PAIR_ROWS) {
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int r = r0 + 4 * u;
+      const bool in = w + r < w1;   // rows past the slab are never summed
+      As[r][col] = in ? topic_stage<METRIC, false>(((double)na[u] + a.beta_a) / da) : 0.0;
+      Bs[r][col] = in ? topic_stage<METRIC, true>(((double)nb[u] + a.beta_b) / db) : 0.0;
+    }
+    __syncthreads();
+    if (w + TOPIC_PAIR_ROWS < w1) fetch(w + TOPIC_PAIR_ROWS);
+    const int rows = (int)min((int64_t)TOPIC_PAIR_ROWS, w1 - w);
+    for (int r = 0; r < rows; ++r) {
+      double x[4], y[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        x[i] = As[r][ty + 16 * i];
+        y[i] = Bs[r][tx + 16 * i];
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] += topic_term<METRIC>(x[i], y[j]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int ai = ta * 64 + ty + 16 * i;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int bj = tb * 64 + tx + 16 * j;
+      if (ai < a.K && bj < a.K2) a.part[((size_t)s * a.K + ai) * a.K2 + bj] = acc[i][j];
+    }
+  }
+}
+
+// One thread per cell of the result: the slabs in order, then the metric's
+// closing expression.  With `upper` the cell below the diagonal takes the
+// pair sums of its mirror (the closing expressions are symmetric in the two
+// topics' sums), so the matrix is bit-symmetric; v + 0.0 leaves no -0.0.
+__global__ __launch_bounds__(256) void k_topic_dist_final(const TopicPairArgs a) {
+  const int64_t cell = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (cell >= (int64_t)a.K * a.K2) return;
+  const int ra = (int)(cell / a.K2), rb = (int)(cell % a.K2);
+  if (a.self && ra == rb) {
+    a.out[cell] = a.metric == TOPIC_COSINE ? 1.0 : 0.0;
+    return;
+  }
+  const bool mirror = a.upper && ra > rb;
+  const int i = mirror ? rb : ra, j = mirror ? ra : rb;
+  double S = 0.0;
+  for (int s = 0; s < a.slabs; ++s) S += a.part[((size_t)s * a.K + i) * a.K2 + j];
+  const double a2 = a.tot_a[i], al = a.tot_a[a.Kp + i], b2 = a.tot_b[j], bl = a.tot_b[a.Kp2 + j];
+  double v;
+  if (a.metric == TOPIC_COSINE)
+    v = S / sqrt(a2 * b2);
+  else if (a.metric == TOPIC_HELLINGER)
+    v = sqrt(fmin(1.0, 0.5 * S));
+  else if (a.metric == TOPIC_JS)
+    v = fmax(0.0, 0.5 * ((al + bl) - S));
+  else
+    v = al - S;
+  a.out[cell] = v + 0.0;
+}
+
+// The smaller of two (key, id) pairs over the wave (every lane gets it).
+__device__ __forceinline__ void wave_min_key_id(unsigned long long& k, int& id) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t hi = (uint32_t)__shfl_xor((int)(k >> 32), o), lo = (uint32_t)__shfl_xor((int)(uint32_t)k, o);
+    const unsigned long long ok = ((unsigned long long)hi << 32) | lo;
+    const int oid = __shfl_xor(id, o);
+    if (ok < k || (ok == k && oid < id)) {
+      k = ok;
+      id = oid;
+    }
+  }
+}
+
+// lda_topic_nearest: one wave per row.  The order key of a value is its bit
+// pattern made monotone (sign bit flipped for v >= 0, all bits for v < 0;
+// complemented for a descending order), and the candidates are ordered by
+// (key, topic id), so equal values go to the lower id.  Round i takes the
+// smallest pair above round i - 1's: lane l scans topics l, l + 64, ...,
+// then a wave-wide minimum.  Nothing is kept between rounds but the last
+// pair; an exhausted row fills id -1, NaN.
+__global__ __launch_bounds__(64) void k_topic_nearest(const TopicNearestArgs a) {
+  const int lane = threadIdx.x, row = blockIdx.x;
+  const double* __restrict__ m = a.mat + (size_t)row * a.K2;
+  constexpr int NONE = 0x7FFFFFFF;
+  unsigned long long pk = 0;
+  int pid = -1;   // every candidate is above (0, -1)
+  for (int i = 0; i < a.n; ++i) {
+    unsigned long long bk = ~0ull;
+    int bid = NONE;
+    for (int b = lane; b < a.K2; b += 64) {
+      if (a.self && b == row) continue;
+      unsigned long long u = (unsigned long long)__double_as_longlong(m[b] + 0.0);
+      u = (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+      if (a.descending) u = ~u;
+      const bool after = u > pk || (u == pk && b > pid);
+      if (after && (u < bk || (u == bk && b < bid))) {
+        bk = u;
+        bid = b;
+      }
+    }
+    wave_min_key_id(bk, bid);
+    if (lane == 0) {
+      a.topics[(size_t)row * a.n + i] = bid == NONE ? -1 : bid;
+      a.values[(size_t)row * a.n + i] = bid == NONE ? __longlong_as_double(0x7FF8000000000000ll) : m[bid];
+    }
+    pk = bk;
+    pid = bid;
+  }
+}
+
 // lda_heldout_loglik: inv[k] = 1 / (nwsum[k] + V beta) in fp64, 0 for the
 // padded topics.
 __global__ __launch_bounds__(256) void k_heldout_inv(const int32_t* __restrict__ nwsum, double vbeta, int32_t K,
@@ -4757,6 +4965,49 @@ hipError_t launch_word_stats(const WordStatsArgs& a, hipStream_t st) {
   if (e != hipSuccess || a.V < 1) return e;
   if (a.slabs < 1 || (int64_t)a.slabs * a.slab_rows < a.V) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_sumsq, dim3(a.slabs, a.Kp / 64), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
+static bool topic_slabs_ok(int32_t V, int32_t slabs, int32_t slab_rows) {
+  return V >= 1 && slabs >= 1 && slabs <= TOPIC_MAX_SLABS && slab_rows >= 1 && (int64_t)slabs * slab_rows >= V &&
+         (int64_t)(slabs - 1) * slab_rows < V;
+}
+
+hipError_t launch_topic_sums(const TopicSumsArgs& a, hipStream_t st) {
+  if (!topic_slabs_ok(a.V, a.slabs, a.slab_rows) || a.Kp < 64 || a.Kp % 64) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_topic_sums, dim3(a.slabs, a.Kp / 64), dim3(64), 0, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_topic_sums_reduce, dim3((2 * a.Kp + 255) / 256), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_topic_pairs(const TopicPairArgs& a, hipStream_t st) {
+  if (!topic_slabs_ok(a.V, a.slabs, a.slab_rows) || a.K < 1 || a.K2 < 1 || a.K > a.Kp || a.K2 > a.Kp2 || a.Kp % 64 ||
+      a.Kp2 % 64 || (a.upper && !a.self) || (a.self && (a.K != a.K2 || a.Kp != a.Kp2)))
+    return hipErrorInvalidValue;
+  const dim3 grid(a.Kp2 / 64, a.Kp / 64, a.slabs);
+  switch (a.metric) {
+    case TOPIC_COSINE: hipLaunchKernelGGL(k_topic_pairs<TOPIC_COSINE>, grid, dim3(256), 0, st, a); break;
+    case TOPIC_HELLINGER: hipLaunchKernelGGL(k_topic_pairs<TOPIC_HELLINGER>, grid, dim3(256), 0, st, a); break;
+    case TOPIC_JS: hipLaunchKernelGGL(k_topic_pairs<TOPIC_JS>, grid, dim3(256), 0, st, a); break;
+    case TOPIC_KL: hipLaunchKernelGGL(k_topic_pairs<TOPIC_KL>, grid, dim3(256), 0, st, a); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_topic_dist_final(const TopicPairArgs& a, hipStream_t st) {
+  if (a.K < 1 || a.K2 < 1 || a.slabs < 1 || a.metric < TOPIC_COSINE || a.metric > TOPIC_KL)
+    return hipErrorInvalidValue;
+  const int64_t cells = (int64_t)a.K * a.K2;
+  hipLaunchKernelGGL(k_topic_dist_final, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_topic_nearest(const TopicNearestArgs& a, hipStream_t st) {
+  if (a.K < 1 || a.K2 < 1 || a.n < 1 || a.n > 64) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_topic_nearest, dim3(a.K), dim3(64), 0, st, a);
   return hipGetLastError();
 }
 

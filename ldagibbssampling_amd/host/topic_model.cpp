@@ -956,6 +956,37 @@ void ParallelTopicModel::topWords(int32_t n, int32_t* word_ids, int32_t* counts)
   check(lda_top_words(shards_->ctx[0], n, word_ids, counts), "lda_top_words");
 }
 
+namespace {
+// the arguments of topicDistances / nearestTopics (n null: no n), in
+// lda_topic_distances' order, before any shard is built
+void checkTopicPair(const ParallelTopicModel& m, const ParallelTopicModel* other, int32_t metric, const int32_t* n,
+                    bool outputs) {
+  if (metric < LDA_TOPIC_COSINE || metric > LDA_TOPIC_KL)
+    raise(LDA_ERR_INVALID_ARG, "metric must be LDA_TOPIC_COSINE, _HELLINGER, _JS or _KL");
+  if (n && (*n < 1 || *n > LDA_TOPIC_NEAREST_MAX)) raise(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_TOPIC_NEAREST_MAX]");
+  if (!outputs) raise(LDA_ERR_INVALID_ARG, "null output");
+  if (other && other->numTypes() != m.numTypes())
+    raise(LDA_ERR_INVALID_ARG, "the two models differ in num_types (V)");
+}
+}  // namespace
+
+void ParallelTopicModel::topicDistances(ParallelTopicModel* other, int32_t metric, double* out) {
+  checkTopicPair(*this, other, metric, nullptr, out != nullptr);
+  ensureShards();
+  if (other && other != this) other->ensureShards();
+  check(lda_topic_distances(shards_->ctx[0], other ? other->shards_->ctx[0] : nullptr, metric, out),
+        "lda_topic_distances");
+}
+
+void ParallelTopicModel::nearestTopics(ParallelTopicModel* other, int32_t metric, int32_t n, int32_t* topics,
+                                       double* values) {
+  checkTopicPair(*this, other, metric, &n, topics && values);
+  ensureShards();
+  if (other && other != this) other->ensureShards();
+  check(lda_topic_nearest(shards_->ctx[0], other ? other->shards_->ctx[0] : nullptr, metric, n, topics, values),
+        "lda_topic_nearest");
+}
+
 void ParallelTopicModel::docReadout(int32_t mtop, int64_t M, const int64_t* docs, int32_t* out0, int32_t* out1) {
   if (M < 0) raise(LDA_ERR_INVALID_ARG, "bad sizes");
   const int64_t D = numDocs();
@@ -1953,6 +1984,17 @@ lda_status ldatm_get_topic_probabilities(ldatm* m, int64_t doc, double* out) {
 lda_status ldatm_top_words(ldatm* m, int32_t n, int32_t* word_ids, int32_t* counts) {
   TM_CHECK(m);
   return guard([&] { m->model.topWords(n, word_ids, counts); });
+}
+
+lda_status ldatm_topic_distances(ldatm* m, ldatm* other, int32_t metric, double* out) {
+  TM_CHECK(m);
+  return guard([&] { m->model.topicDistances(other ? &other->model : nullptr, metric, out); });
+}
+
+lda_status ldatm_nearest_topics(ldatm* m, ldatm* other, int32_t metric, int32_t n, int32_t* topics,
+                                double* values) {
+  TM_CHECK(m);
+  return guard([&] { m->model.nearestTopics(other ? &other->model : nullptr, metric, n, topics, values); });
 }
 
 lda_status ldatm_doc_top_topics(ldatm* m, int32_t mtop, int64_t M, const int64_t* docs, int32_t* topics,

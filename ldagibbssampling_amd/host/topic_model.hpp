@@ -130,6 +130,14 @@ class ParallelTopicModel {
   // diagnosticsFinish: out [K LDATM_DIAG_COLUMNS]; word_ids [K n] or null
   void topicDiagnostics(int32_t n, double* out, int32_t* word_ids);
 
+  // ---- topic distances and nearest topics ----------------
+  // lda_topic_distances / lda_topic_nearest on shard 0 of this model against
+  // shard 0 of `other` (null: this model); every shard holds the same global
+  // counts.  out [K * K2]; topics / values [K * n].  The arguments are checked
+  // before any shard is built.
+  void topicDistances(ParallelTopicModel* other, int32_t metric, double* out);
+  void nearestTopics(ParallelTopicModel* other, int32_t metric, int32_t n, int32_t* topics, double* values);
+
   // ---- outputs -------------------------------------------------------
   std::string documentTopics(double threshold, int32_t max);
   std::string displayTopWords(int32_t num_words, bool using_new_lines);

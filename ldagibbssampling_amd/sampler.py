@@ -474,6 +474,48 @@ class GibbsSampler:
                                                 shares.ctypes.data, sumsq.ctypes.data), "lda_topic_word_stats")
         return counts, totals, shares, sumsq
 
+    def _other_sampler(self, other):
+        """The native handle of the other side of a topic comparison (None:
+        this sampler), checked before any native call."""
+        if other is None or other is self:
+            return None, self.K
+        if not isinstance(other, GibbsSampler):
+            raise ValueError(f"other must be a GibbsSampler or None, not {type(other).__name__}")
+        if other.V != self.V:
+            raise ValueError(f"other holds {other.V} word types, this sampler {self.V}")
+        return other._h, other.K
+
+    def topic_distances(self, metric="jensen_shannon", other=None) -> np.ndarray:
+        """lda_topic_distances: the float64 (K, K2) matrix of a distance between
+        the smoothed topics phi_k(w) = (nw[w, k] + beta) / (nwsum[k] + V beta)
+        of this sampler (rows) and of `other` (columns; None: this sampler,
+        K2 = K), computed on the device.  metric: "cosine" (a similarity),
+        "hellinger", "jensen_shannon" (nats) or "kullback_leibler"
+        (KL(row || column)), or the LDA_TOPIC_* integer.  Each side uses its own
+        beta; both must hold the same V, and word ids must mean the same words
+        on both sides: aligning vocabularies is the caller's job."""
+        m = capi.topic_metric(metric)
+        oh, K2 = self._other_sampler(other)
+        out = np.zeros((self.K, K2), dtype=np.float64)
+        capi.check(self._L.lda_topic_distances(self._h, oh, m, out.ctypes.data), "lda_topic_distances")
+        return out
+
+    def nearest_topics(self, n: int, metric="jensen_shannon", other=None):
+        """lda_topic_nearest: per topic of this sampler the n nearest topics of
+        `other` (None: this sampler, the topic itself left out), selected on
+        the device from topic_distances' matrix: value ascending (cosine:
+        descending), equal values by ascending topic id.  Returns (topics
+        int32 (K, n), values float64 (K, n)); slots past the last candidate
+        hold -1 / NaN."""
+        n = capi.topic_nearest_n(n)
+        m = capi.topic_metric(metric)
+        oh, _ = self._other_sampler(other)
+        topics = np.zeros((self.K, n), dtype=np.int32)
+        values = np.zeros((self.K, n), dtype=np.float64)
+        capi.check(self._L.lda_topic_nearest(self._h, oh, m, n, topics.ctypes.data, values.ctypes.data),
+                   "lda_topic_nearest")
+        return topics, values
+
     def heldout_loglik(self, theta, doc_off, words):
         """lda_heldout_loglik: the log likelihood of the scored tokens of Dh
         held-out documents (doc_off[Dh + 1], words) under their topic

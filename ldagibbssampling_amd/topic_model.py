@@ -75,6 +75,8 @@ TM_SIGNATURES = {
     "ldatm_top_words": (_i32, [_vp, _i32, _vp, _vp]),
     "ldatm_doc_top_topics": (_i32, [_vp, _i32, C.c_int64, _vp, _vp, _vp]),
     "ldatm_doc_counts": (_i32, [_vp, C.c_int64, _vp, _vp]),
+    "ldatm_topic_distances": (_i32, [_vp, _vp, _i32, _vp]),
+    "ldatm_nearest_topics": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "ldatm_topic_codocuments": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp]),
     "ldatm_topic_statistics": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ldatm_diagnostics_finish": (_i32, [_i32, _i32, _i32, C.c_double, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -446,6 +448,49 @@ class ParallelTopicModel:
         _check(self._L.ldatm_doc_top_topics(self._h, n, M, ids.ctypes.data if ids is not None and M else None,
                                             topics.ctypes.data, cnt.ctypes.data), "docTopTopics")
         return topics, cnt
+
+    # ------------------------------- topic distances
+    def _other_model(self, other):
+        """(native handle or None, K2) of the other side of a topic
+        comparison, checked before any native call."""
+        if other is None or other is self:
+            return None, self.numTopics
+        if not isinstance(other, ParallelTopicModel):
+            raise ValueError(f"other must be a ParallelTopicModel or None, not {type(other).__name__}")
+        mine = None if self.alphabet is None else self.alphabet.toArray()
+        theirs = None if other.alphabet is None else other.alphabet.toArray()
+        if mine != theirs:
+            raise ValueError("the two models' alphabets differ: word ids must mean the same words in both")
+        return other._h, other.numTopics
+
+    def topicDistances(self, other=None, metric="jensen_shannon") -> np.ndarray:
+        """ldatm_topic_distances: the float64 (K, K2) matrix of a distance
+        between this model's smoothed topics (rows) and `other`'s (columns;
+        None: this model), computed on the device from the global counts.
+        metric: "cosine" (a similarity), "hellinger", "jensen_shannon" (nats),
+        "kullback_leibler" (KL(row || column)), or the LDA_TOPIC_* integer.
+        `other`'s alphabet must equal this model's -- word ids must mean the
+        same words; aligning two vocabularies is the caller's job."""
+        m = capi.topic_metric(metric)
+        oh, K2 = self._other_model(other)
+        out = np.zeros((self.numTopics, K2), np.float64)
+        _check(self._L.ldatm_topic_distances(self._h, oh, m, out.ctypes.data), "topicDistances")
+        return out
+
+    def nearestTopics(self, n: int, other=None, metric="jensen_shannon"):
+        """ldatm_nearest_topics: per topic the n nearest topics of `other`
+        (None: this model, the topic itself left out), selected on the device:
+        value ascending (cosine: descending), ties by ascending topic id.
+        Returns (topics int32 (K, n), values float64 (K, n)); -1 / NaN past the
+        last candidate.  `other` as topicDistances takes it."""
+        n = capi.topic_nearest_n(n)
+        m = capi.topic_metric(metric)
+        oh, _ = self._other_model(other)
+        topics = np.zeros((self.numTopics, n), np.int32)
+        values = np.zeros((self.numTopics, n), np.float64)
+        _check(self._L.ldatm_nearest_topics(self._h, oh, m, n, topics.ctypes.data, values.ctypes.data),
+               "nearestTopics")
+        return topics, values
 
     # ------------------------------- topic diagnostics (DESIGN 9e)
     def topicCodocuments(self, word_ids, props=()):
