@@ -609,6 +609,53 @@ lda_status lda_topic_word_stats(lda_ctx* ctx, int32_t n, const int32_t* word_ids
                                 int32_t* counts /*[K*n]*/, int64_t* totals /*[K*n]*/,
                                 double* share_sums /*[K*n]*/, uint64_t* sumsq /*[K]*/);
 
+/* lda_word_cooccurrences: the counts behind reference-corpus topic coherence
+ * (UMass, UCI / PMI, NPMI), by plain co-occurrence in a corpus, whatever the
+ * tokens' topics.  word_ids are K lists as
+ * lda_topic_codocuments takes them (1 <= n <= LDA_DIAG_WORDS_MAX, -1 = an
+ * empty slot, no id twice in one list; a word may stand in any number of
+ * topics' lists, at different slots).
+ * The corpus: doc_off == NULL is THIS shard's own training documents, already
+ * on the device (Dh and words are ignored); otherwise Dh documents in host
+ * memory, document d's tokens words[doc_off[d] - doc_off[0] ..
+ * doc_off[d + 1] - doc_off[0]), ids in [-1, V): -1 is a token outside the
+ * alphabet, which keeps its position in a window and matches nothing.
+ * The units: window == 0, every document with at least one token is one
+ * unit; window == W >= 1, a document of L >= 1 tokens gives max(1, L - W + 1)
+ * units, the token ranges [s, s + W) clipped to the document.  A document
+ * without tokens is no unit.
+ * cooc: one packed lower triangle per topic, int64, in lda_topic_codocuments'
+ * layout: cell (i, j), j <= i, of topic k at cooc[k * n (n + 1) / 2 +
+ * i (i + 1) / 2 + j] = units that hold a token of word_ids[k, i] and a token
+ * of word_ids[k, j]; the diagonal is the units holding that one word; cells
+ * of an empty slot are 0.  *units = the number of units.  Integer counts:
+ * exact, independent of the grid, of the chunks and of Dh's other documents,
+ * two corpora's results add, and a call repeats bit for bit.  The block
+ * counters are 32-bit and moved to the 64-bit result before they can reach
+ * 2^29, whatever the corpus.
+ * The call reads neither z nor the counts: a pending delta is NOT an error,
+ * and the call leaves all model state untouched.
+ * Errors, all checked on the host before any device work:
+ * LDA_ERR_INVALID_ARG for a NULL ctx, word_ids, cooc or units, n or the
+ * lists as above, window outside [0, LDA_COOC_WINDOW_MAX], and with a host
+ * corpus Dh < 0, a non-monotone doc_off, NULL words when there are tokens, or
+ * an id outside [-1, V); LDA_ERR_UNSUPPORTED for K >= 2^25.  Dh = 0 succeeds
+ * with zeros.
+ * Device scratch is grow-only and kept by the context: the words' membership
+ * rows (4 (V + 1) + 4 K n bytes), the result (8 K n (n + 1) / 2 bytes: 68 MiB
+ * at K = 4096, n = 64), and for a host corpus one chunk of whole documents:
+ * at most 2^23 tokens (32 MiB of ids; a single longer document goes alone and
+ * takes 4 bytes per token) and 2^20 documents (8 MiB of offsets).  Waits for
+ * the context's stream. */
+#define LDA_COOC_WINDOW_MAX 256
+lda_status lda_word_cooccurrences(lda_ctx* ctx, int32_t n, const int32_t* word_ids /*[K*n]*/, int32_t window,
+                                  int64_t Dh, const int64_t* doc_off, const int32_t* words,
+                                  int64_t* cooc /*[K*n(n+1)/2]*/, int64_t* units);
+/* Test hook: lda_word_cooccurrences cuts a host corpus into chunks of at most
+ * `tokens` tokens instead of 2^23 (0 = the default; a longer document goes
+ * alone). */
+void lda_debug_cooc_chunk_tokens(int64_t tokens);
+
 /* Topic distances and nearest topics, within one model or between two, on the
  * device from the global int32 nw rows and nwsum.  other ==
  * NULL or other == ctx is SELF mode (K2 = K); else CROSS mode: topic a of ctx
@@ -786,7 +833,8 @@ void lda_debug_fail_host_alloc(int32_t nth);
  * lda_doc_top_topics and lda_doc_counts, then lda_topic_codocuments and
  * lda_topic_word_stats, then lda_left_to_right (with its test hook
  * lda_debug_ltr_chunk_cells), then lda_topic_distances, lda_topic_nearest
- * and lda_topic_distance_slabs came later and only add symbols, so the
+ * and lda_topic_distance_slabs, then lda_word_cooccurrences (with its test
+ * hook lda_debug_cooc_chunk_tokens) came later and only add symbols, so the
  * version stays 8. */
 #define LDA_ABI_VERSION 8
 const char* lda_version(void);

@@ -290,6 +290,68 @@ lda_status ldatm_diagnostics_finish(int32_t K, int32_t V, int32_t n, double beta
 lda_status ldatm_topic_diagnostics(ldatm* m, int32_t n, double* out /*[K*LDATM_DIAG_COLUMNS]*/,
                                    int32_t* word_ids /*[K*n] or NULL*/);
 
+/* Reference-corpus topic coherence: UMass (Mimno et al. 2011),
+ * UCI / PMI (Newman et al. 2010) and NPMI (Lau et al. 2014) of each topic's
+ * top words, by plain co-occurrence in a corpus -- whatever the tokens'
+ * topics -- counted on the device (lda_word_cooccurrences).  The corpus is
+ * the training corpus or any corpus over the same alphabet.
+ *
+ * ldatm_word_cooccurrences: lda_word_cooccurrences with the caller's lists
+ * word_ids[K*n] (-1 = empty slot) and window (0 = documents are the units,
+ * W >= 1 = sliding windows of W tokens).  doc_off == NULL: the training
+ * corpus; every shard counts its own documents and the results are summed
+ * (Dh and words are ignored).  Otherwise Dh documents in host memory, ids in
+ * [-1, V) (-1 = a token outside the alphabet), counted by shard 0 alone.
+ * cooc[K * n(n+1)/2] (cell (i, j), j <= i, of a topic at i(i+1)/2 + j) and
+ * *units.  Integer sums: the result does not depend on the number of shards,
+ * bit for bit.  It reads neither z nor the counts and leaves the model's
+ * state untouched.
+ * Errors (checked before any device work, against the model's K and V):
+ * LDA_ERR_INVALID_ARG for a NULL model, word_ids, cooc or units, n outside
+ * [1, LDA_DIAG_WORDS_MAX], an id outside [-1, V), the same id twice in one
+ * topic's list, window outside [0, LDA_COOC_WINDOW_MAX], and with a host
+ * corpus Dh < 0, a non-monotone doc_off, NULL words when there are tokens or
+ * a token id outside [-1, V).
+ *
+ * ldatm_coherence_finish: host only, no model and no device.  From the
+ * triangles cooc[K * n(n+1)/2] and N = units it writes, per topic, sums[k] =
+ * the sum of the measure's term over the kept pairs and pairs[k] = their
+ * number; the topic's coherence is sums[k] / pairs[k], and 0.0 when no pair is
+ * kept.  With D(i) = the diagonal cell (i, i), D(i,j) = the cell (i, j), every
+ * count converted to fp64, natural logarithms, the pairs (i, j), j < i, added
+ * in fp64 with i ascending and then j ascending from 0.0, and a pair skipped
+ * when D(i) = 0 or D(j) = 0 (an empty slot has D = 0):
+ *   LDATM_COHERENCE_UMASS  log((D(i,j) + eps) / D(j));           default eps 1
+ *   LDATM_COHERENCE_UCI    log((D(i,j) / N + eps) / ((D(i) / N) * (D(j) / N))),
+ *                          also skipped when D(i,j) = N;     default eps 1e-12
+ *   LDATM_COHERENCE_NPMI   the UCI term / (-log(D(i,j) / N + eps)), the same
+ *                          skips and default
+ * epsilon < 0 selects the measure's default.  N = 0 gives all zeros.
+ * LDA_ERR_INVALID_ARG for K < 1, units < 0, n outside [1, LDA_DIAG_WORDS_MAX],
+ * a measure outside [0, 2] or a NULL argument.
+ *
+ * ldatm_topic_coherence: ldatm_top_words(n) on the device, then
+ * ldatm_word_cooccurrences with those lists, then ldatm_coherence_finish:
+ * values[K] = sums / pairs (0.0 without a kept pair) and pairs[K]; the lists
+ * in word_ids_out[K*n] and the counts in cooc_out[K * n(n+1)/2] unless NULL;
+ * *units.  Errors: LDA_ERR_INVALID_ARG for a NULL model, values, pairs or
+ * units, a measure, n or window out of range, or a bad host corpus as above
+ * (all before any device work). */
+#define LDATM_COHERENCE_UMASS 0
+#define LDATM_COHERENCE_UCI 1
+#define LDATM_COHERENCE_NPMI 2
+lda_status ldatm_word_cooccurrences(ldatm* m, int32_t n, const int32_t* word_ids /*[K*n]*/, int32_t window,
+                                    int64_t Dh, const int64_t* doc_off, const int32_t* words,
+                                    int64_t* cooc /*[K*n(n+1)/2]*/, int64_t* units);
+lda_status ldatm_coherence_finish(int32_t K, int32_t n, int32_t measure, double epsilon,
+                                  const int64_t* cooc /*[K*n(n+1)/2]*/, int64_t units, double* sums /*[K]*/,
+                                  int64_t* pairs /*[K]*/);
+lda_status ldatm_topic_coherence(ldatm* m, int32_t measure, int32_t n, int32_t window,
+                                 double epsilon /*<0 = the measure's default*/, int64_t Dh, const int64_t* doc_off,
+                                 const int32_t* words, double* values /*[K]*/, int64_t* pairs /*[K]*/,
+                                 int32_t* word_ids_out /*[K*n] or NULL*/, int64_t* cooc_out /*[K*n(n+1)/2] or NULL*/,
+                                 int64_t* units);
+
 /* printDocumentTopics(File) (threshold 0, max -1 = all) and its text:
  * "#doc source topic proportion ...", then per document
  * "<doc> <source|null-source> <topic> <weight> ... \n" (weights descending,

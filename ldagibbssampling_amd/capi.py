@@ -37,6 +37,8 @@ TOP_TOPICS_MAX = 64
 # LDA_DIAG_WORDS_MAX / LDA_DIAG_PROPS_MAX of lda_mi355x.h
 DIAG_WORDS_MAX = 64
 DIAG_PROPS_MAX = 8
+# LDA_COOC_WINDOW_MAX of lda_mi355x.h
+COOC_WINDOW_MAX = 256
 # LDA_LTR_MAX_PARTICLES / LDA_LTR_MAX_DOC_TOKENS of lda_mi355x.h
 LTR_MAX_PARTICLES = 1024
 LTR_MAX_DOC_TOKENS = 4096
@@ -175,6 +177,8 @@ SIGNATURES = {
     "lda_doc_counts": (C.c_int32, [_vp, C.c_int64, C.c_int64, _vp, _vp]),
     "lda_topic_codocuments": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
     "lda_topic_word_stats": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "lda_word_cooccurrences": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int32, C.c_int64, _vp, _vp, _vp, _vp]),
+    "lda_debug_cooc_chunk_tokens": (None, [C.c_int64]),
     "lda_topic_distances": (C.c_int32, [_vp, _vp, C.c_int32, _vp]),
     "lda_topic_nearest": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
     "lda_topic_distance_slabs": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),

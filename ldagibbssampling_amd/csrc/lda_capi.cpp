@@ -231,6 +231,14 @@ constexpr int64_t LTR_CELLS = int64_t(1) << 22;
 constexpr int64_t LTR_DOCS = int64_t(1) << 20;
 static_assert((int64_t)LDA_LTR_MAX_PARTICLES * LDA_LTR_MAX_DOC_TOKENS <= LTR_CELLS, "a document alone must fit a chunk");
 int64_t g_ltr_cells = 0;   // lda_debug_ltr_chunk_cells (0: LTR_CELLS)
+// lda_word_cooccurrences: a host corpus goes up in chunks of whole documents,
+// at most COOC_TOKENS tokens (32 MiB of ids; a single longer document goes
+// alone) and COOC_DOCS documents each; k_cooc's blocks (slabs x topic groups)
+// per CU, each of which adds its nonzero cells to the result once
+constexpr int64_t COOC_TOKENS = int64_t(1) << 23;
+constexpr int64_t COOC_DOCS = int64_t(1) << 20;
+constexpr int64_t COOC_BLOCKS_PER_CU = 4;
+int64_t g_cooc_tokens = 0;   // lda_debug_cooc_chunk_tokens (0: COOC_TOKENS)
 // lda_top_words' slab pass: at least TOP_WORDS_SLAB_ROWS rows per slab (a
 // slab's list warms up over its first rows), at most TOP_WORDS_WAVES (slab,
 // topic group) waves, which bounds the slab lists at TOP_WORDS_WAVES * 64 * n
@@ -361,6 +369,13 @@ struct lda_ctx {
   unsigned long long* dg_out = nullptr;
   double* dg_shares = nullptr;
   size_t dg_cap[4] = {};
+  // lda_word_cooccurrences: grow-only scratch -- the membership rows (offsets
+  // [V + 1] and entries), the int64 result, a host corpus chunk's ids and
+  // offsets
+  int32_t *cc_moff = nullptr, *cc_mem = nullptr, *cc_words = nullptr;
+  unsigned long long* cc_out = nullptr;
+  int64_t* cc_off = nullptr;
+  size_t cc_cap[5] = {};
   // 16-bit rows of the snapshot (LDA_SAMPLER_DENSE)
   uint16_t* nw16 = nullptr;
   uint8_t* wide = nullptr;
@@ -512,6 +527,7 @@ struct lda_ctx {
                     (void*)ro_lists, (void*)ro_out, (void*)ro_docs,
                     (void*)ro_part, (void*)ro_sums, (void*)ro_mat, (void*)ro_vals, (void*)ro_ids,
                     (void*)dg_ids, (void*)dg_table, (void*)dg_out, (void*)dg_shares,
+                    (void*)cc_moff, (void*)cc_mem, (void*)cc_words, (void*)cc_out, (void*)cc_off,
                     (void*)perm, (void*)items, (void*)warm.range_doc, (void*)steady.range_doc,
                     (void*)big.tab, (void*)big.tab_m1, (void*)big.F, (void*)big.pfx, (void*)big.scal})
       if (p) (void)hipFree(p);
@@ -2494,6 +2510,8 @@ hipError_t grow_bytes(void** ptr, size_t* cap, size_t bytes) {
   grow_bytes(reinterpret_cast<void**>(&(ptr)), &(c)->ro_cap[(slot)], (n) * sizeof(*(ptr)))
 #define dg_need(c, ptr, n, slot) \
   grow_bytes(reinterpret_cast<void**>(&(ptr)), &(c)->dg_cap[(slot)], (n) * sizeof(*(ptr)))
+#define cc_need(c, ptr, n, slot) \
+  grow_bytes(reinterpret_cast<void**>(&(ptr)), &(c)->cc_cap[(slot)], (n) * sizeof(*(ptr)))
 
 // the document arguments lda_score_docs takes, checked the same way
 lda_status check_doc_list(const lda_ctx* c, int64_t doc_begin, int64_t M, const int64_t* docs) {
@@ -2760,6 +2778,123 @@ lda_status lda_topic_word_stats(lda_ctx* c, int32_t n, const int32_t* word_ids, 
   HIP_TRY(hipMemcpyAsync(totals, a.totals, sizeof(int64_t) * cells, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(share_sums, a.share_sums, sizeof(double) * cells, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(sumsq, a.sumsq, sizeof(uint64_t) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LDA_OK;
+  });
+}
+
+void lda_debug_cooc_chunk_tokens(int64_t tokens) { g_cooc_tokens = tokens > 0 ? tokens : 0; }
+
+lda_status lda_word_cooccurrences(lda_ctx* c, int32_t n, const int32_t* word_ids, int32_t window, int64_t Dh,
+                                  const int64_t* doc_off, const int32_t* words_in, int64_t* cooc, int64_t* units) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (lda_status s = check_word_lists(c, n, word_ids); s != LDA_OK) return s;
+  if (!cooc || !units) return fail(LDA_ERR_INVALID_ARG, "null output");
+  if (window < 0 || window > LDA_COOC_WINDOW_MAX)
+    return fail(LDA_ERR_INVALID_ARG, "window must be in [0, LDA_COOC_WINDOW_MAX]");
+  const bool host = doc_off != nullptr;
+  if (host) {
+    if (Dh < 0) return fail(LDA_ERR_INVALID_ARG, "bad sizes");
+    for (int64_t d = 1; d <= Dh; ++d)
+      if (doc_off[d] < doc_off[d - 1]) return fail(LDA_ERR_INVALID_ARG, "doc_off not monotone");
+    const int64_t N = doc_off[Dh] - doc_off[0];
+    if (N > 0 && !words_in) return fail(LDA_ERR_INVALID_ARG, "words is null");
+    for (int64_t i = 0; i < N; ++i)
+      if (words_in[i] < -1 || words_in[i] >= c->V) return fail(LDA_ERR_INVALID_ARG, "word id out of range [-1, V)");
+  }
+  const int32_t K = c->K;
+  // a membership is (topic << 6) | slot in an int32
+  if (K >= (1 << 25)) return fail(LDA_ERR_UNSUPPORTED, "co-occurrences: 2^25 or more topics");
+  const int64_t D = host ? Dh : c->D;
+  const int64_t* off = host ? doc_off : c->doc_off_h.data();
+  int64_t u = 0;
+  for (int64_t d = 0; d < D; ++d) {
+    const int64_t L = off[d + 1] - off[d];
+    if (L > 0) u += window == 0 ? 1 : std::max<int64_t>(1, L - window + 1);
+  }
+  const size_t tri = (size_t)n * (n + 1) / 2, cells = (size_t)K * tri;
+  std::fill(cooc, cooc + cells, 0);
+  *units = u;
+  if (u == 0) return LDA_OK;
+  // the words' membership rows: offsets by word, entries ascending within a row
+  std::vector<int32_t> moff = host_vector<int32_t>((size_t)c->V + 1);
+  for (size_t i = 0; i < (size_t)K * (size_t)n; ++i)
+    if (word_ids[i] >= 0) ++moff[(size_t)word_ids[i] + 1];
+  for (int32_t w = 0; w < c->V; ++w) moff[(size_t)w + 1] += moff[(size_t)w];
+  const size_t entries = (size_t)moff[(size_t)c->V];
+  std::vector<int32_t> mem = host_vector<int32_t>(std::max<size_t>(1, entries));
+  {
+    std::vector<int32_t> at(moff.begin(), moff.end() - 1);
+    for (int32_t k = 0; k < K; ++k)
+      for (int32_t i = 0; i < n; ++i) {
+        const int32_t w = word_ids[(size_t)k * n + i];
+        if (w >= 0) mem[(size_t)at[(size_t)w]++] = (k << 6) | i;
+      }
+  }
+  lda::CoocArgs a{};
+  a.K = K;
+  a.n = n;
+  a.window = window;
+  a.group_topics = lda::cooc_group_topics(K, n, lda::COOC_WAVES);
+  const int64_t groups = (K + a.group_topics - 1) / a.group_topics;
+  if (groups > 65535) return fail(LDA_ERR_UNSUPPORTED, "co-occurrences: more than 65535 topic groups");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(cc_need(c, c->cc_moff, moff.size(), 0));
+  HIP_TRY(cc_need(c, c->cc_mem, mem.size(), 1));
+  HIP_TRY(cc_need(c, c->cc_out, cells, 2));
+  HIP_TRY(hipMemcpyAsync(c->cc_moff, moff.data(), sizeof(int32_t) * moff.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->cc_mem, mem.data(), sizeof(int32_t) * mem.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(c->cc_out, 0, sizeof(unsigned long long) * cells, c->stream));
+  a.moff = c->cc_moff;
+  a.mem = c->cc_mem;
+  a.out = c->cc_out;
+  // a wave takes a tile of 64 documents (window 0) or a document
+  auto slabs = [&](int64_t docs) {
+    const int64_t items = window == 0 ? (docs + 63) / 64 : docs;
+    return (int)std::min<int64_t>(std::max<int64_t>(1, (items + lda::COOC_WAVES - 1) / lda::COOC_WAVES),
+                                  std::max<int64_t>(1, COOC_BLOCKS_PER_CU * c->cus / groups));
+  };
+  if (!host) {
+    a.words = c->words;
+    a.doc_off = c->doc_off;
+    a.D = D;
+    HIP_TRY(lda::launch_cooc(a, slabs(D), c->stream));
+  } else {
+    // chunks of whole documents: at most COOC_DOCS documents and tok_cap
+    // tokens each (a single longer document goes alone)
+    const int64_t tok_cap = g_cooc_tokens > 0 ? g_cooc_tokens : COOC_TOKENS;
+    const int64_t first = doc_off[0];
+    std::vector<int64_t> cut(1, 0);
+    int64_t max_tokens = 1, max_docs = 1;
+    for (int64_t d0 = 0; d0 < Dh;) {
+      int64_t d1 = d0 + 1;
+      while (d1 < Dh && d1 - d0 < COOC_DOCS && doc_off[d1 + 1] - doc_off[d0] <= tok_cap) ++d1;
+      max_tokens = std::max(max_tokens, doc_off[d1] - doc_off[d0]);
+      max_docs = std::max(max_docs, d1 - d0);
+      cut.push_back(d1);
+      d0 = d1;
+    }
+    HIP_TRY(cc_need(c, c->cc_words, (size_t)max_tokens, 3));
+    HIP_TRY(cc_need(c, c->cc_off, (size_t)max_docs + 1, 4));
+    std::vector<int64_t> rel = host_vector<int64_t>((size_t)max_docs + 1);
+    a.words = c->cc_words;
+    a.doc_off = c->cc_off;
+    for (size_t ch = 0; ch + 1 < cut.size(); ++ch) {
+      const int64_t d0 = cut[ch], dn = cut[ch + 1] - d0;
+      const int64_t w0 = doc_off[d0] - first, wn = doc_off[d0 + dn] - first - w0;
+      if (wn == 0) continue;   // empty documents only: no unit
+      for (int64_t d = 0; d <= dn; ++d) rel[(size_t)d] = doc_off[d0 + d] - first - w0;
+      HIP_TRY(hipMemcpyAsync(c->cc_off, rel.data(), sizeof(int64_t) * (size_t)(dn + 1), hipMemcpyHostToDevice,
+                             c->stream));
+      HIP_TRY(hipMemcpyAsync(c->cc_words, words_in + w0, sizeof(int32_t) * (size_t)wn, hipMemcpyHostToDevice,
+                             c->stream));
+      a.D = dn;
+      HIP_TRY(lda::launch_cooc(a, slabs(dn), c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));   // the scratch (and rel) is reused by the next chunk
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(cooc, c->cc_out, sizeof(int64_t) * cells, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return LDA_OK;
   });

@@ -332,6 +332,37 @@ struct WordStatsArgs {
   unsigned long long* sumsq;       // [K], zeroed
 };
 hipError_t launch_word_stats(const WordStatsArgs& a, hipStream_t st);
+// lda_word_cooccurrences (k_cooc): units of a corpus that hold
+// two listed words, whatever their topics.  A word's memberships are a CSR
+// row: mem[moff[w] .. moff[w + 1]) = (topic << 6) | slot, ascending (so by
+// topic).  Grid (slabs, topic groups), `waves` waves per block; a wave takes a
+// tile of up to 64 units -- 64 consecutive documents (window == 0) or 64
+// consecutive window starts of one document -- and keeps, per (topic of the
+// group, slot), the 64-bit mask of the tile's units that hold the word: a
+// token of document j sets bit j; a token at position q of a window tile sets
+// the starts [q - window + 1, q].  Cell (i, j) then grows by
+// popcount(mask i & mask j).  LDS: per wave a slot mask per topic and the unit
+// masks [Gt (n + 1)] of 8 bytes, and the block's int32 triangles [Gt][T].
+constexpr size_t COOC_LDS_BYTES = 64 * 1024;
+constexpr int COOC_WAVES = 4;
+// a wave moves the block's triangles to the result whenever it has counted
+// this many units since it last did: a cell then holds less than COOC_WAVES x
+// (COOC_FLUSH_UNITS + 64) = 2^28 + 256 at any time, whatever the corpus
+constexpr int32_t COOC_FLUSH_UNITS = 1 << 26;
+constexpr int cooc_group_topics(int K, int n, int waves) {
+  const int per = 8 * waves * (n + 1) + 4 * (n * (n + 1) / 2), g = (int)(COOC_LDS_BYTES / per);
+  return g < K ? g : K;
+}
+struct CoocArgs {
+  const int32_t* words;              // ids in [-1, V); -1 matches nothing
+  const int64_t* doc_off;            // [D + 1] into words
+  int64_t D;
+  const int32_t* moff;               // [V + 1]
+  const int32_t* mem;                // [moff[V]]
+  int32_t K, n, window, group_topics;
+  unsigned long long* out;           // [K * n (n + 1) / 2], zeroed by the caller before the first launch
+};
+hipError_t launch_cooc(const CoocArgs& a, int slabs, hipStream_t st);
 // lda_heldout_loglik (k_doc_completion): the scored tokens of Dh held-out
 // documents against the int32 nw rows.  A wave takes a document's tokens in
 // batches of doc_completion_batch(C): 64 up to C = 8, 16 above (the batch's

@@ -5169,5 +5169,140 @@ hipError_t launch_recount(int32_t Kp, const uint32_t* perm, const int32_t* zw, c
   return hipGetLastError();
 }
 
+// lda_word_cooccurrences: out[k][i, j] += units of the corpus holding a token
+// of word ids[k, i] and a token of ids[k, j] (lda_kernels.h, CoocArgs).  Block
+// (slab s, group g) owns topics [g Gt, (g + 1) Gt); its waves take tiles of up
+// to 64 units.  Staging: the wave's lanes walk the tile's tokens; a token's
+// word row is searched for the group's first topic and every membership
+// (topic, slot) in the group ORs the token's unit bits into the wave's
+// smask[topic][slot] and the slot's bit into present[topic] (LDS ors: repeats
+// and neighbours fold here).  Then lane t takes topic t: for every pair of
+// present slots j <= i it adds popcount(smask[i] & smask[j]) to the block's
+// triangle (an LDS add: the waves share the triangles) and clears what it
+// read.  A wave that has counted COOC_FLUSH_UNITS units since its last flush
+// moves the block's triangles to the result with an LDS exchange per cell, so
+// no add is lost and none counted twice whichever waves add meanwhile; the
+// block does the same once at the end: one 64-bit integer atomic per nonzero
+// cell, consecutive lanes on consecutive cells.  Integers only.
+__global__ __launch_bounds__(64 * COOC_WAVES) void k_cooc(const CoocArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long cc_lds[];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int n = a.n, Gt = a.group_topics, T = n * (n + 1) / 2, W = a.window;
+  const int k0 = (int)blockIdx.y * Gt, gt = min(Gt, a.K - k0);
+  unsigned long long* present = cc_lds + (size_t)wid * Gt * (n + 1);
+  unsigned long long* smask = present + Gt;
+  int32_t* tri = reinterpret_cast<int32_t*>(cc_lds + (size_t)COOC_WAVES * Gt * (n + 1));
+  for (int i = threadIdx.x; i < gt * T; i += 64 * COOC_WAVES) tri[i] = 0;
+  for (int i = lane; i < Gt * (n + 1); i += 64) present[i] = 0;
+  __syncthreads();
+  const int32_t* __restrict__ words = a.words;
+  const int64_t* __restrict__ doc_off = a.doc_off;
+  const int32_t* __restrict__ moff = a.moff;
+  const int32_t* __restrict__ mem = a.mem;
+  unsigned long long* __restrict__ out = a.out + (size_t)k0 * T;
+  const int32_t first = k0 << 6;
+  int32_t since = 0;   // units this wave has counted since it last flushed
+  auto stage = [&](int32_t w, unsigned long long bits) {
+    if (w < 0) return;
+    const int32_t e = moff[w + 1];
+    int32_t lo = moff[w], hi = e;
+    while (lo < hi) {   // the row's first membership at or past topic k0
+      const int32_t mid = (lo + hi) >> 1;
+      if (mem[mid] < first) lo = mid + 1; else hi = mid;
+    }
+    for (; lo < e; ++lo) {
+      const int32_t m = mem[lo], kl = (m >> 6) - k0;
+      if (kl >= gt) break;
+      atomicOr(&smask[kl * n + (m & 63)], bits);
+      atomicOr(&present[kl], 1ull << (m & 63));
+    }
+  };
+  auto count = [&](int units) {
+    wave_lds_fence();
+    for (int t = lane; t < gt; t += 64) {
+      const unsigned long long m = present[t];
+      if (m == 0) continue;
+      present[t] = 0;
+      unsigned long long* sm = smask + t * n;
+      int32_t* cell = tri + t * T;
+      for (unsigned long long mi = m; mi; mi &= mi - 1) {
+        const int i = __builtin_ctzll(mi);
+        const unsigned long long si = sm[i];
+        int32_t* row = cell + i * (i + 1) / 2;
+        for (unsigned long long mj = m & ((2ull << i) - 1); mj; mj &= mj - 1) {
+          const int j = __builtin_ctzll(mj);
+          const int c = __popcll(si & sm[j]);
+          if (c) atomicAdd(&row[j], c);
+        }
+      }
+      for (unsigned long long mi = m; mi; mi &= mi - 1) sm[__builtin_ctzll(mi)] = 0;
+    }
+    wave_lds_fence();
+    since += units;
+    if (since >= COOC_FLUSH_UNITS) {
+      for (int i = lane; i < gt * T; i += 64) {
+        const int32_t v = atomicExch(&tri[i], 0);
+        if (v) atomicAdd(&out[i], (unsigned long long)v);
+      }
+      since = 0;
+    }
+  };
+  const int64_t stride = (int64_t)gridDim.x * COOC_WAVES;
+  if (W == 0) {
+    // a tile is 64 consecutive documents; the lanes walk their tokens as one
+    // range and find a token's document among the tile's ends
+    const int64_t tiles = (a.D + 63) >> 6;
+    for (int64_t tile = (int64_t)blockIdx.x * COOC_WAVES + wid; tile < tiles; tile += stride) {
+      const int64_t d0 = tile << 6;
+      const int nd = (int)min((int64_t)64, a.D - d0);
+      const int64_t* end = doc_off + d0 + 1;
+      const int64_t t1 = end[nd - 1];
+      for (int64_t i = doc_off[d0] + lane; i < t1; i += 64) {
+        int lo = 0, hi = nd - 1;
+        while (lo < hi) {   // the first document whose end lies past token i
+          const int mid = (lo + hi) >> 1;
+          if (end[mid] <= i) lo = mid + 1; else hi = mid;
+        }
+        stage(words[i], 1ull << lo);
+      }
+      count(nd);
+    }
+  } else {
+    // a wave takes a document; a tile is 64 consecutive window starts, lane q
+    // of a pass the token at position q of the tile's span
+    for (int64_t d = (int64_t)blockIdx.x * COOC_WAVES + wid; d < a.D; d += stride) {
+      const int64_t t0 = doc_off[d], L = doc_off[d + 1] - t0;
+      if (L <= 0) continue;
+      const int64_t units = max((int64_t)1, L - W + 1);
+      for (int64_t s0 = 0; s0 < units; s0 += 64) {
+        const int ns = (int)min((int64_t)64, units - s0);
+        const int span = (int)min(L - s0, (int64_t)(ns + W - 1));
+        for (int q = lane; q < span; q += 64) {
+          const int lo = max(0, q - W + 1), hi = min(q, ns - 1);
+          const unsigned long long run = hi - lo == 63 ? ~0ull : (1ull << (hi - lo + 1)) - 1;
+          stage(words[t0 + s0 + q], run << lo);
+        }
+        count(ns);
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < gt * T; i += 64 * COOC_WAVES) {
+    const int32_t v = tri[i];
+    if (v) atomicAdd(&out[i], (unsigned long long)v);
+  }
+}
+
+hipError_t launch_cooc(const CoocArgs& a, int slabs, hipStream_t st) {
+  if (a.n < 1 || a.n > DIAG_WORDS_MAX || a.K < 1 || slabs < 1 || a.window < 0 || a.group_topics < 1 ||
+      a.group_topics != cooc_group_topics(a.K, a.n, COOC_WAVES))
+    return hipErrorInvalidValue;
+  if (a.D <= 0) return hipSuccess;
+  const int Gt = a.group_topics, groups = (a.K + Gt - 1) / Gt;
+  // per wave a slot mask and n unit masks per topic, then the triangles: at most COOC_LDS_BYTES
+  const size_t lds = (size_t)Gt * (8 * (size_t)COOC_WAVES * (a.n + 1) + 4 * (size_t)(a.n * (a.n + 1) / 2));
+  hipLaunchKernelGGL(k_cooc, dim3(slabs, groups), dim3(64 * COOC_WAVES), lds, st, a);
+  return hipGetLastError();
+}
 
 }  // namespace lda

@@ -1049,21 +1049,26 @@ void ParallelTopicModel::docCounts(int64_t M, const int64_t* docs, int32_t* nd) 
 namespace {
 // Mallet's TopicModelDiagnostics thresholds (its DEFAULT_DOC_PROPORTIONS)
 constexpr double DIAG_PROPS[LDATM_DIAG_PROPS] = {0.01, 0.02, 0.05, 0.1, 0.2, 0.3, 0.5};
+
+// the sampler ABI's checks of K word lists, against the model's K and V
+void checkWordLists(int32_t K, int32_t V, int32_t n, const int32_t* word_ids) {
+  if (n < 1 || n > LDA_DIAG_WORDS_MAX) raise(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_DIAG_WORDS_MAX]");
+  if (!word_ids) raise(LDA_ERR_INVALID_ARG, "null word_ids");
+  for (int32_t k = 0; k < K; ++k) {
+    const int32_t* l = word_ids + (size_t)k * n;
+    for (int32_t i = 0; i < n; ++i) {
+      if (l[i] < -1 || l[i] >= V) raise(LDA_ERR_INVALID_ARG, "word_ids: id outside [-1, V)");
+      for (int32_t j = 0; l[i] >= 0 && j < i; ++j)
+        if (l[j] == l[i]) raise(LDA_ERR_INVALID_ARG, "word_ids: the same id twice in one topic's list");
+    }
+  }
+}
 }  // namespace
 
 void ParallelTopicModel::topicCodocuments(int32_t n, const int32_t* word_ids, int32_t P, const double* props,
                                           int64_t* codoc, int64_t* doc_stats) {
   // lda_topic_codocuments' checks, against the model's K and V, before any device work
-  if (n < 1 || n > LDA_DIAG_WORDS_MAX) raise(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_DIAG_WORDS_MAX]");
-  if (!word_ids) raise(LDA_ERR_INVALID_ARG, "null word_ids");
-  for (int32_t k = 0; k < K_; ++k) {
-    const int32_t* l = word_ids + (size_t)k * n;
-    for (int32_t i = 0; i < n; ++i) {
-      if (l[i] < -1 || l[i] >= V_) raise(LDA_ERR_INVALID_ARG, "word_ids: id outside [-1, V)");
-      for (int32_t j = 0; l[i] >= 0 && j < i; ++j)
-        if (l[j] == l[i]) raise(LDA_ERR_INVALID_ARG, "word_ids: the same id twice in one topic's list");
-    }
-  }
+  checkWordLists(K_, V_, n, word_ids);
   if (P < 0 || P > LDA_DIAG_PROPS_MAX) raise(LDA_ERR_INVALID_ARG, "P must be in [0, LDA_DIAG_PROPS_MAX]");
   if (P > 0 && !props) raise(LDA_ERR_INVALID_ARG, "null props");
   for (int32_t i = 0; i < P; ++i)
@@ -1189,6 +1194,105 @@ void ParallelTopicModel::topicDiagnostics(int32_t n, double* out, int32_t* word_
   diagnosticsFinish(K_, V_, n, beta_, nwsum.data(), max_doc_len_, hist.data(), ids.data(), counts.data(),
                     totals.data(), shares.data(), sumsq.data(), codoc.data(), stats.data(), out);
   if (word_ids) std::copy(ids.begin(), ids.end(), word_ids);
+}
+
+namespace {
+// lda_word_cooccurrences' checks of the window and a host corpus, against the
+// model's V, before any device work
+void checkCooccurrenceCorpus(int32_t V, int32_t window, int64_t Dh, const int64_t* doc_off, const int32_t* words) {
+  if (window < 0 || window > LDA_COOC_WINDOW_MAX)
+    raise(LDA_ERR_INVALID_ARG, "window must be in [0, LDA_COOC_WINDOW_MAX]");
+  if (!doc_off) return;
+  if (Dh < 0) raise(LDA_ERR_INVALID_ARG, "bad sizes");
+  for (int64_t d = 1; d <= Dh; ++d)
+    if (doc_off[d] < doc_off[d - 1]) raise(LDA_ERR_INVALID_ARG, "doc_off not monotone");
+  const int64_t N = doc_off[Dh] - doc_off[0];
+  if (N > 0 && !words) raise(LDA_ERR_INVALID_ARG, "words is null");
+  for (int64_t i = 0; i < N; ++i)
+    if (words[i] < -1 || words[i] >= V) raise(LDA_ERR_INVALID_ARG, "word id out of range [-1, V)");
+}
+}  // namespace
+
+void ParallelTopicModel::wordCooccurrences(int32_t n, const int32_t* word_ids, int32_t window, int64_t Dh,
+                                           const int64_t* doc_off, const int32_t* words, int64_t* cooc,
+                                           int64_t* units) {
+  checkWordLists(K_, V_, n, word_ids);
+  if (!cooc || !units) raise(LDA_ERR_INVALID_ARG, "null output");
+  checkCooccurrenceCorpus(V_, window, Dh, doc_off, words);
+  ensureShards();
+  if (doc_off) {
+    check(lda_word_cooccurrences(shards_->ctx[0], n, word_ids, window, Dh, doc_off, words, cooc, units),
+          "lda_word_cooccurrences");
+    return;
+  }
+  const size_t tri = (size_t)K_ * ((size_t)n * (n + 1) / 2);
+  std::fill(cooc, cooc + tri, 0);
+  *units = 0;
+  std::vector<int64_t> part(tri);
+  for (auto c : shards_->ctx) {
+    int64_t u = 0;
+    check(lda_word_cooccurrences(c, n, word_ids, window, 0, nullptr, nullptr, part.data(), &u),
+          "lda_word_cooccurrences");
+    for (size_t i = 0; i < tri; ++i) cooc[i] += part[i];
+    *units += u;
+  }
+}
+
+void coherenceFinish(int32_t K, int32_t n, int32_t measure, double epsilon, const int64_t* cooc, int64_t units,
+                     double* sums, int64_t* pairs) {
+  if (K < 1 || units < 0) raise(LDA_ERR_INVALID_ARG, "bad sizes");
+  if (n < 1 || n > LDA_DIAG_WORDS_MAX) raise(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_DIAG_WORDS_MAX]");
+  if (measure < LDATM_COHERENCE_UMASS || measure > LDATM_COHERENCE_NPMI)
+    raise(LDA_ERR_INVALID_ARG, "measure must be LDATM_COHERENCE_UMASS, _UCI or _NPMI");
+  if (!cooc) raise(LDA_ERR_INVALID_ARG, "null cooc");
+  if (!sums || !pairs) raise(LDA_ERR_INVALID_ARG, "null output");
+  const double eps = epsilon >= 0.0 ? epsilon : measure == LDATM_COHERENCE_UMASS ? 1.0 : 1e-12;
+  const double N = (double)units;
+  const size_t tri = (size_t)n * (n + 1) / 2;
+  for (int32_t k = 0; k < K; ++k) {
+    const int64_t* C = cooc + (size_t)k * tri;
+    double sum = 0.0;
+    int64_t kept = 0;
+    for (int32_t i = 1; units > 0 && i < n; ++i) {
+      const int64_t Di = C[(size_t)i * (i + 1) / 2 + i];
+      if (Di == 0) continue;
+      for (int32_t j = 0; j < i; ++j) {
+        const int64_t Dj = C[(size_t)j * (j + 1) / 2 + j], Dij = C[(size_t)i * (i + 1) / 2 + j];
+        if (Dj == 0) continue;
+        if (measure == LDATM_COHERENCE_UMASS) {
+          sum += std::log(((double)Dij + eps) / (double)Dj);
+        } else {
+          if (Dij == units) continue;
+          const double p = (double)Dij / N + eps;
+          const double uci = std::log(p / (((double)Di / N) * ((double)Dj / N)));
+          sum += measure == LDATM_COHERENCE_UCI ? uci : uci / -std::log(p);
+        }
+        ++kept;
+      }
+    }
+    sums[k] = sum;
+    pairs[k] = kept;
+  }
+}
+
+void ParallelTopicModel::topicCoherence(int32_t measure, int32_t n, int32_t window, double epsilon, int64_t Dh,
+                                        const int64_t* doc_off, const int32_t* words, double* values, int64_t* pairs,
+                                        int32_t* word_ids_out, int64_t* cooc_out, int64_t* units) {
+  if (measure < LDATM_COHERENCE_UMASS || measure > LDATM_COHERENCE_NPMI)
+    raise(LDA_ERR_INVALID_ARG, "measure must be LDATM_COHERENCE_UMASS, _UCI or _NPMI");
+  if (n < 1 || n > LDA_DIAG_WORDS_MAX) raise(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_DIAG_WORDS_MAX]");
+  checkCooccurrenceCorpus(V_, window, Dh, doc_off, words);
+  if (!values || !pairs || !units) raise(LDA_ERR_INVALID_ARG, "null output");
+  ensureShards();
+  const size_t cells = (size_t)K_ * (size_t)n, tri = (size_t)K_ * ((size_t)n * (n + 1) / 2);
+  std::vector<int32_t> ids(cells), counts(cells);
+  std::vector<int64_t> cooc(tri);
+  topWords(n, ids.data(), counts.data());
+  wordCooccurrences(n, ids.data(), window, Dh, doc_off, words, cooc.data(), units);
+  coherenceFinish(K_, n, measure, epsilon, cooc.data(), *units, values, pairs);
+  for (int32_t k = 0; k < K_; ++k) values[k] = pairs[k] > 0 ? values[k] / (double)pairs[k] : 0.0;
+  if (word_ids_out) std::copy(ids.begin(), ids.end(), word_ids_out);
+  if (cooc_out) std::copy(cooc.begin(), cooc.end(), cooc_out);
 }
 
 std::vector<double> ParallelTopicModel::getTopicProbabilities(int64_t doc) {
@@ -2034,6 +2138,27 @@ lda_status ldatm_diagnostics_finish(int32_t K, int32_t V, int32_t n, double beta
 lda_status ldatm_topic_diagnostics(ldatm* m, int32_t n, double* out, int32_t* word_ids) {
   TM_CHECK(m);
   return guard([&] { m->model.topicDiagnostics(n, out, word_ids); });
+}
+
+lda_status ldatm_word_cooccurrences(ldatm* m, int32_t n, const int32_t* word_ids, int32_t window, int64_t Dh,
+                                    const int64_t* doc_off, const int32_t* words, int64_t* cooc, int64_t* units) {
+  TM_CHECK(m);
+  return guard([&] { m->model.wordCooccurrences(n, word_ids, window, Dh, doc_off, words, cooc, units); });
+}
+
+lda_status ldatm_coherence_finish(int32_t K, int32_t n, int32_t measure, double epsilon, const int64_t* cooc,
+                                  int64_t units, double* sums, int64_t* pairs) {
+  return guard([&] { lda_host::coherenceFinish(K, n, measure, epsilon, cooc, units, sums, pairs); });
+}
+
+lda_status ldatm_topic_coherence(ldatm* m, int32_t measure, int32_t n, int32_t window, double epsilon, int64_t Dh,
+                                 const int64_t* doc_off, const int32_t* words, double* values, int64_t* pairs,
+                                 int32_t* word_ids_out, int64_t* cooc_out, int64_t* units) {
+  TM_CHECK(m);
+  return guard([&] {
+    m->model.topicCoherence(measure, n, window, epsilon, Dh, doc_off, words, values, pairs, word_ids_out, cooc_out,
+                            units);
+  });
 }
 
 lda_status ldatm_document_topics_text(ldatm* m, double threshold, int32_t max, char* buf, size_t cap,

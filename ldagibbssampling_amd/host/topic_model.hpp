@@ -34,6 +34,12 @@ void diagnosticsFinish(int32_t K, int32_t V, int32_t n, double beta, const int32
                        const int64_t* totals, const double* share_sums, const uint64_t* sumsq, const int64_t* codoc,
                        const int64_t* doc_stats, double* out);
 
+// Reference-corpus coherence from co-occurrence counts (host only, no device;
+// ldatm_coherence_finish of lda_topic_model.h states the three expressions):
+// sums [K] over the kept pairs and their number pairs [K]
+void coherenceFinish(int32_t K, int32_t n, int32_t measure, double epsilon, const int64_t* cooc, int64_t units,
+                     double* sums, int64_t* pairs);
+
 class ParallelTopicModel {
  public:
   ParallelTopicModel(int32_t num_topics, double alpha_sum, double beta);
@@ -129,6 +135,19 @@ class ParallelTopicModel {
   // topicStatistics, the shards' topicDocCounts of the current z and
   // diagnosticsFinish: out [K LDATM_DIAG_COLUMNS]; word_ids [K n] or null
   void topicDiagnostics(int32_t n, double* out, int32_t* word_ids);
+
+  // ---- reference-corpus coherence ------------------------
+  // lda_word_cooccurrences with the caller's lists: on the training corpus
+  // (doc_off null) every shard counts its own documents and the results add;
+  // a host corpus goes to shard 0 alone.  cooc [K n(n+1)/2], *units
+  void wordCooccurrences(int32_t n, const int32_t* word_ids, int32_t window, int64_t Dh, const int64_t* doc_off,
+                         const int32_t* words, int64_t* cooc, int64_t* units);
+  // topWords(n), wordCooccurrences and coherenceFinish: values [K] (the mean
+  // over the kept pairs, 0 without one) and pairs [K]; word_ids_out [K n] and
+  // cooc_out [K n(n+1)/2] may be null; epsilon < 0: the measure's default
+  void topicCoherence(int32_t measure, int32_t n, int32_t window, double epsilon, int64_t Dh, const int64_t* doc_off,
+                      const int32_t* words, double* values, int64_t* pairs, int32_t* word_ids_out, int64_t* cooc_out,
+                      int64_t* units);
 
   // ---- topic distances and nearest topics ----------------
   // lda_topic_distances / lda_topic_nearest on shard 0 of this model against

@@ -474,6 +474,37 @@ class GibbsSampler:
                                                 shares.ctypes.data, sumsq.ctypes.data), "lda_topic_word_stats")
         return counts, totals, shares, sumsq
 
+    def word_cooccurrences(self, word_ids, window: int = 0, doc_off=None, words=None):
+        """lda_word_cooccurrences: units of a corpus that hold two listed
+        words, whatever their topics.  word_ids[K, n] (-1 = empty slot).
+        window 0: every non-empty document is a unit; window W >= 1: the
+        max(1, L - W + 1) ranges of W tokens of a document of L tokens.
+        doc_off None: this shard's training documents; else a host corpus
+        (doc_off[Dh + 1], words with ids in [-1, V), -1 matching nothing).
+        Returns (cooc[K, n (n + 1) / 2] int64, each topic's packed lower
+        triangle, cell (i, j), j <= i, at i (i + 1) / 2 + j; units).  It reads
+        neither z nor the counts, so it may run between sample and apply."""
+        ids, n = self._word_lists(word_ids)
+        if not 0 <= int(window) <= capi.COOC_WINDOW_MAX:
+            raise ValueError(f"window must be in [0, {capi.COOC_WINDOW_MAX}]")
+        off = w = None
+        Dh = 0
+        if doc_off is not None:
+            off = np.ascontiguousarray(doc_off, dtype=np.int64).reshape(-1)
+            if len(off) < 1:
+                raise ValueError("doc_off must hold Dh + 1 offsets")
+            Dh = len(off) - 1
+            w = np.ascontiguousarray(words if words is not None else [], dtype=np.int32).reshape(-1)
+            if len(w) < off[-1] - off[0]:
+                raise ValueError("words is shorter than doc_off says")
+        cooc = np.zeros((self.K, n * (n + 1) // 2), dtype=np.int64)
+        units = C.c_int64(0)
+        capi.check(self._L.lda_word_cooccurrences(self._h, n, ids.ctypes.data, int(window), Dh,
+                                                  off.ctypes.data if off is not None else None,
+                                                  w.ctypes.data if w is not None and len(w) else None,
+                                                  cooc.ctypes.data, C.addressof(units)), "lda_word_cooccurrences")
+        return cooc, int(units.value)
+
     def _other_sampler(self, other):
         """The native handle of the other side of a topic comparison (None:
         this sampler), checked before any native call."""

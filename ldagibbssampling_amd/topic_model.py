@@ -82,6 +82,10 @@ TM_SIGNATURES = {
     "ldatm_diagnostics_finish": (_i32, [_i32, _i32, _i32, C.c_double, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                         _vp, _vp]),
     "ldatm_topic_diagnostics": (_i32, [_vp, _i32, _vp, _vp]),
+    "ldatm_word_cooccurrences": (_i32, [_vp, _i32, _vp, _i32, C.c_int64, _vp, _vp, _vp, _vp]),
+    "ldatm_coherence_finish": (_i32, [_i32, _i32, _i32, C.c_double, _vp, C.c_int64, _vp, _vp]),
+    "ldatm_topic_coherence": (_i32, [_vp, _i32, _i32, _i32, C.c_double, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _vp]),
     "ldatm_print_document_topics": (_i32, [_vp, C.c_char_p, C.c_double, _i32]),
     "ldatm_document_topics_text": (_i32, [_vp, C.c_double, _i32, _vp, C.c_size_t,
                                           C.POINTER(C.c_size_t)]),
@@ -542,6 +546,80 @@ class ParallelTopicModel:
         # the triangles themselves, for the same lists (one more document pass)
         return TopicDiagnostics(self, out, ids, self.topicCodocuments(ids)[0])
 
+    # ------------------------------- reference-corpus coherence
+    def _reference(self, reference):
+        """(Dh, doc_off or None, words or None) of a coherence corpus: None is
+        the training corpus; an InstanceList goes up from the host, its tokens
+        outside the model's alphabet as -1."""
+        if reference is None:
+            return 0, None, None
+        if not isinstance(reference, InstanceList):
+            raise ValueError(f"reference must be an InstanceList or None, not {type(reference).__name__}")
+        off, w = _flatten(list(reference))
+        V = self._shape()[1]
+        if self.alphabet is not None and reference.alphabet is not self.alphabet:
+            # the reference's ids mean its own alphabet's words
+            to = np.array([self.alphabet.lookupIndex(e, False) for e in reference.alphabet.toArray()] + [-1], np.int32)
+            w = to[np.where((w >= 0) & (w < len(to) - 1), w, len(to) - 1)]
+        w = np.ascontiguousarray(np.where((w >= 0) & (w < V), w, -1), np.int32)
+        return len(off) - 1, off, w
+
+    def wordCooccurrences(self, word_ids, window: int = 0, reference=None):
+        """ldatm_word_cooccurrences: units of a corpus (window 0: its non-empty
+        documents; W >= 1: its windows of W tokens) that hold two words of a
+        topic's list word_ids[K, n] (-1 = empty slot), whatever the tokens'
+        topics, counted on the device.  reference None: the training corpus
+        (every shard's documents, summed); else an InstanceList.  Returns
+        (cooc[K, n (n + 1) / 2] int64, units)."""
+        ids = np.ascontiguousarray(word_ids, dtype=np.int32)
+        if ids.ndim != 2 or ids.shape[0] != self.numTopics:
+            raise ValueError("word_ids must be [K, n]")
+        n = ids.shape[1]
+        if not 1 <= n <= capi.DIAG_WORDS_MAX:
+            raise ValueError(f"n must be in [1, {capi.DIAG_WORDS_MAX}]")
+        if not 0 <= int(window) <= capi.COOC_WINDOW_MAX:
+            raise ValueError(f"window must be in [0, {capi.COOC_WINDOW_MAX}]")
+        Dh, off, w = self._reference(reference)
+        cooc = np.zeros((self.numTopics, n * (n + 1) // 2), np.int64)
+        units = C.c_int64(0)
+        _check(self._L.ldatm_word_cooccurrences(self._h, n, ids.ctypes.data, int(window), Dh,
+                                                off.ctypes.data if off is not None else None,
+                                                w.ctypes.data if w is not None and len(w) else None,
+                                                cooc.ctypes.data, C.addressof(units)), "wordCooccurrences")
+        return cooc, int(units.value)
+
+    def getCoherence(self, measure: str = "c_npmi", numTopWords: int = 10, window=None, reference=None,
+                     epsilon=None) -> "TopicCoherence":
+        """Coherence of each topic's numTopWords top words by co-occurrence in
+        a corpus (ldatm_topic_coherence): measure "u_mass" (Mimno 2011),
+        "c_uci" (Newman 2010) or "c_npmi" (Lau 2014).  window None: the
+        measure's customary units, documents (0) for u_mass and windows of 10
+        tokens for c_uci / c_npmi.  reference None: the training corpus; else
+        an InstanceList (tokens outside the model's alphabet match nothing).
+        epsilon None: 1 for u_mass, 1e-12 otherwise."""
+        if measure not in COHERENCE_MEASURES:
+            raise ValueError(f"measure must be one of {sorted(COHERENCE_MEASURES)}, not {measure!r}")
+        n = int(numTopWords)
+        if not 1 <= n <= capi.DIAG_WORDS_MAX:
+            raise ValueError(f"numTopWords must be in [1, {capi.DIAG_WORDS_MAX}]")
+        window = (0 if measure == "u_mass" else 10) if window is None else int(window)
+        if not 0 <= window <= capi.COOC_WINDOW_MAX:
+            raise ValueError(f"window must be in [0, {capi.COOC_WINDOW_MAX}]")
+        eps = -1.0 if epsilon is None else float(epsilon)
+        if epsilon is not None and not eps >= 0.0:
+            raise ValueError("epsilon must be >= 0")
+        Dh, off, w = self._reference(reference)
+        K = self.numTopics
+        values, pairs = np.zeros(K, np.float64), np.zeros(K, np.int64)
+        ids, cooc = np.zeros((K, n), np.int32), np.zeros((K, n * (n + 1) // 2), np.int64)
+        units = C.c_int64(0)
+        _check(self._L.ldatm_topic_coherence(self._h, COHERENCE_MEASURES[measure], n, window, eps, Dh,
+                                             off.ctypes.data if off is not None else None,
+                                             w.ctypes.data if w is not None and len(w) else None,
+                                             values.ctypes.data, pairs.ctypes.data, ids.ctypes.data, cooc.ctypes.data,
+                                             C.addressof(units)), "getCoherence")
+        return TopicCoherence(self, measure, window, epsilon, values, pairs, ids, cooc, int(units.value))
+
     def topTopics(self, docs=None, n: int = 10):
         """The n heaviest topics of the documents `docs` (global ids; None =
         all): (topics[M, n] int32, weights[M, n] fp64), weights
@@ -701,6 +779,51 @@ def diagnostics_finish(V: int, beta: float, nwsum, topic_doc_counts, word_ids, c
     _check(load_tm().ldatm_diagnostics_finish(K, int(V), n, float(beta), p[0], a[1].shape[1] - 1, *p[1:],
                                               out.ctypes.data), "ldatm_diagnostics_finish")
     return out
+
+
+# LDATM_COHERENCE_* of lda_topic_model.h
+COHERENCE_MEASURES = {"u_mass": 0, "c_uci": 1, "c_npmi": 2}
+
+
+def coherence_finish(measure, cooc, units: int, n: int | None = None, epsilon=None):
+    """ldatm_coherence_finish (host only, no device): (sums[K] fp64 over the
+    kept pairs, pairs[K] int64) of a measure ("u_mass", "c_uci", "c_npmi" or
+    the LDATM_COHERENCE_* integer) from the triangles cooc[K, n (n + 1) / 2]
+    and the number of units; epsilon None: the measure's default."""
+    m = COHERENCE_MEASURES.get(measure, measure) if isinstance(measure, str) else int(measure)
+    if m not in COHERENCE_MEASURES.values():
+        raise ValueError(f"measure must be one of {sorted(COHERENCE_MEASURES)}, not {measure!r}")
+    c = np.ascontiguousarray(cooc, np.int64)
+    if c.ndim != 2 or c.shape[0] < 1:
+        raise ValueError("cooc must be [K, n (n + 1) / 2]")
+    K, T = c.shape
+    if n is None:
+        n = int(round((np.sqrt(8.0 * T + 1.0) - 1.0) / 2.0))
+    if n * (n + 1) // 2 != T:
+        raise ValueError("cooc must be [K, n (n + 1) / 2]")
+    sums, pairs = np.zeros(K, np.float64), np.zeros(K, np.int64)
+    _check(load_tm().ldatm_coherence_finish(K, int(n), m, -1.0 if epsilon is None else float(epsilon), c.ctypes.data,
+                                            int(units), sums.ctypes.data, pairs.ctypes.data),
+           "ldatm_coherence_finish")
+    return sums, pairs
+
+
+class TopicCoherence:
+    """What ParallelTopicModel.getCoherence returns: values [K] (each topic's
+    mean term over its kept pairs, 0 without one), sums and pairs [K], mean
+    (over the topics with a kept pair), wordIds [K, n] and topWords (the lists
+    the counts were taken over), cooc [K, n (n + 1) / 2] (the packed
+    co-occurrence triangles) and units."""
+
+    def __init__(self, model, measure, window, epsilon, values, pairs, word_ids, cooc, units):
+        self.measure, self.window = measure, window
+        self.values, self.pairs = values, pairs
+        self.sums = coherence_finish(measure, cooc, units, word_ids.shape[1], epsilon)[0]
+        self.wordIds, self.cooc, self.units = word_ids, cooc, units
+        name = (lambda w: w) if model.alphabet is None else model.alphabet.lookupObject
+        self.topWords = [[name(int(w)) for w in row if w >= 0] for row in word_ids]
+        kept = pairs > 0
+        self.mean = float(values[kept].mean()) if kept.any() else 0.0
 
 
 class TopicDiagnostics:
