@@ -347,7 +347,8 @@ lda_status lda_log_likelihood(lda_ctx* ctx, double* out); /* doc_part + word_par
  * are enqueued on the context's stream, and the result is collected later
  * (ParallelTopicModel.estimate()'s "LL/token" every 10 sweeps no longer
  * stops the sweeps).  At most 16 results in flight: a 17th enqueue waits
- * for the oldest, whose ticket then no longer collects (LDA_ERR_STATE). */
+ * for the oldest, whose ticket then no longer collects (LDA_ERR_STATE).  The
+ * blocking calls above take no ticket and push none out of flight. */
 lda_status lda_log_likelihood_enqueue(lda_ctx* ctx, int64_t* ticket);
 lda_status lda_log_likelihood_collect(lda_ctx* ctx, int64_t ticket, double* doc_part, double* word_part);
 

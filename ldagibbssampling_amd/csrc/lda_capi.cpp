@@ -463,6 +463,9 @@ struct lda_ctx {
   static constexpr int LL_SLOTS = 16;
   LLSlot ll[LL_SLOTS];
   int64_t ll_next = 0;
+  // the blocking lda_log_likelihood_parts' own slot: it takes no ticket, so it
+  // cannot push a result in flight out of the ring
+  LLSlot ll_blocking;
   // lda_doc_topic_histograms_accumulate / _take: alpha statistics summed on
   // the device over sampled sweeps [doc lengths (L+1) | topics K x (L+1)]
   int32_t* stat_buf = nullptr;
@@ -537,10 +540,10 @@ struct lda_ctx {
       if (exch_packed[i]) (void)hipFree(exch_packed[i]);
       if (exch_esc[i]) (void)hipFree(exch_esc[i]);
     }
-    for (auto& sl : ll) {
-      if (sl.done) (void)hipEventSynchronize(sl.done);
-      if (sl.host) (void)hipHostFree(sl.host);
-      if (sl.done) (void)hipEventDestroy(sl.done);
+    for (LLSlot* sl : ll_slots()) {
+      if (sl->done) (void)hipEventSynchronize(sl->done);
+      if (sl->host) (void)hipHostFree(sl->host);
+      if (sl->done) (void)hipEventDestroy(sl->done);
     }
     if (stat_buf) (void)hipFree(stat_buf);
     if (chist) (void)hipFree(chist);
@@ -563,6 +566,13 @@ struct lda_ctx {
       if (ev2[i]) (void)hipEventDestroy(ev2[i]);
     }
     if (own_stream) (void)hipStreamDestroy(own_stream);
+  }
+
+  std::vector<LLSlot*> ll_slots() {
+    std::vector<LLSlot*> v;
+    for (auto& sl : ll) v.push_back(&sl);
+    v.push_back(&ll_blocking);
+    return v;
   }
 
   lda::SampleParams params(bool frozen) const {
@@ -1951,13 +1961,14 @@ lda_status lda_set_alpha_beta(lda_ctx* c, const double* alpha, double beta) {
   });
 }
 
-lda_status lda_log_likelihood_enqueue(lda_ctx* c, int64_t* ticket) {
-  return lda_abi::guarded([&]() -> lda_status {
-  if (!c || !ticket) return fail(LDA_ERR_INVALID_ARG, "null argument");
+namespace {
+
+// The log-likelihood kernels and the copies of their partial sums into the
+// slot's pinned memory, enqueued on the context's stream
+lda_status ll_launch(lda_ctx* c, lda_ctx::LLSlot& sl) {
   if (c->pending) return fail(LDA_ERR_STATE, "log likelihood with a pending delta: call lda_apply first");
   HIP_TRY(hipSetDevice(c->device));
   const int nb = c->partial_blocks;
-  lda_ctx::LLSlot& sl = c->ll[c->ll_next % lda_ctx::LL_SLOTS];
   if (!sl.host) {
     HIP_TRY(hipHostMalloc(&sl.host, sizeof(double) * 2 * nb + sizeof(unsigned long long) * nb +
                                         sizeof(int32_t) * c->K, hipHostMallocDefault));
@@ -1986,18 +1997,11 @@ lda_status lda_log_likelihood_enqueue(lda_ctx* c, int64_t* ticket) {
   HIP_TRY(hipEventRecord(sl.done, c->stream));
   sl.alpha_sum = alpha_sum;
   sl.beta = c->beta;
-  sl.ticket = c->ll_next;
-  *ticket = c->ll_next++;
   return LDA_OK;
-  });
 }
 
-lda_status lda_log_likelihood_collect(lda_ctx* c, int64_t ticket, double* doc_part, double* word_part) {
-  return lda_abi::guarded([&]() -> lda_status {
-  if (!c || ticket < 0) return fail(LDA_ERR_INVALID_ARG, "bad argument");
-  lda_ctx::LLSlot& sl = c->ll[ticket % lda_ctx::LL_SLOTS];
-  if (sl.ticket != ticket)
-    return fail(LDA_ERR_STATE, "log-likelihood ticket already collected or overwritten (at most 16 in flight)");
+// Wait for the slot's copies and finish the two sums on the host
+lda_status ll_finish(lda_ctx* c, const lda_ctx::LLSlot& sl, double* doc_part, double* word_part) {
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipEventSynchronize(sl.done));
   const int nb = c->partial_blocks;
@@ -2018,17 +2022,44 @@ lda_status lda_log_likelihood_collect(lda_ctx* c, int64_t ticket, double* doc_pa
   words_ll -= log_gamma_stirling(sl.beta) * (double)nonzero;
   if (doc_part) *doc_part = docs;
   if (word_part) *word_part = words_ll;
+  return LDA_OK;
+}
+
+}  // namespace
+
+lda_status lda_log_likelihood_enqueue(lda_ctx* c, int64_t* ticket) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c || !ticket) return fail(LDA_ERR_INVALID_ARG, "null argument");
+  lda_ctx::LLSlot& sl = c->ll[c->ll_next % lda_ctx::LL_SLOTS];
+  lda_status s = ll_launch(c, sl);
+  if (s) return s;
+  sl.ticket = c->ll_next;
+  *ticket = c->ll_next++;
+  return LDA_OK;
+  });
+}
+
+lda_status lda_log_likelihood_collect(lda_ctx* c, int64_t ticket, double* doc_part, double* word_part) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c || ticket < 0) return fail(LDA_ERR_INVALID_ARG, "bad argument");
+  lda_ctx::LLSlot& sl = c->ll[ticket % lda_ctx::LL_SLOTS];
+  if (sl.ticket != ticket)
+    return fail(LDA_ERR_STATE, "log-likelihood ticket already collected or overwritten (at most 16 in flight)");
+  lda_status s = ll_finish(c, sl, doc_part, word_part);
+  if (s) return s;
   sl.ticket = -1;
   return LDA_OK;
   });
 }
 
+// The blocking call goes through its own slot: the tickets in flight keep
+// theirs, however many blocking calls come between them
 lda_status lda_log_likelihood_parts(lda_ctx* c, double* doc_part, double* word_part) {
   return lda_abi::guarded([&]() -> lda_status {
-  int64_t t = -1;
-  lda_status s = lda_log_likelihood_enqueue(c, &t);
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null argument");
+  lda_status s = ll_launch(c, c->ll_blocking);
   if (s) return s;
-  return lda_log_likelihood_collect(c, t, doc_part, word_part);
+  return ll_finish(c, c->ll_blocking, doc_part, word_part);
   });
 }
 
