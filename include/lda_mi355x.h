@@ -553,6 +553,50 @@ lda_status lda_doc_top_topics(lda_ctx* ctx, int32_t m, int64_t doc_begin, int64_
  * context's stream. */
 lda_status lda_doc_counts(lda_ctx* ctx, int64_t doc_begin, int64_t M, const int64_t* docs, int32_t* nd /*[M*K]*/);
 
+/* lda_topic_top_docs: the documents of THIS shard in which a topic is
+ * heaviest -- the question Mallet's printTopicDocuments answers -- selected on
+ * the device from the shard's current z.  For each topic
+ * k < K (padded topics are never reported) the candidates are the documents d
+ * with at least one token of the topic (n_dk > 0) and a length L_d >=
+ * min_tokens.  They are ordered by the weight
+ *     w(d,k) = ((double) n_dk + smoothing) / ((double) L_d + Ks)
+ * descending, Ks = (double) K * smoothing formed once on the host, one
+ * rounding per operation (IEEE fp64 division; the library is built without
+ * fast-math and with -ffp-contract=off), equal weights by ascending document
+ * id.  The first n candidates go to doc_ids[k*n + i] (shard-local id),
+ * counts[k*n + i] = n_dk and lengths[k*n + i] = L_d, i = 0 .. n-1; slots past
+ * the last candidate hold -1 / 0 / 0, so a topic without tokens is all -1.
+ * 0 < w <= 1 always, so the weight's bit pattern orders as a uint64, and the
+ * pair (weight bits descending, id ascending) is unique per topic: a topic's
+ * best n are one set however the documents are cut into chunks and slabs, and
+ * a call repeats bit for bit.  Integer and fp64 compares only, no atomics on
+ * global memory.
+ * This is this library's definition, not Mallet's: Mallet's sorted sets also
+ * hold the documents with no token of the topic, ranked by the smoothing
+ * alone; here a document that never shows a topic is not one of its top
+ * documents, and a padded slot stays distinguishable.  With smoothing = 0
+ * every one-topic document, one-token ones included, has weight 1.0;
+ * min_tokens drops the short ones.
+ * Errors, all checked on the host before any device work:
+ * LDA_ERR_INVALID_ARG for a NULL ctx or output, n outside
+ * [1, LDA_TOPIC_DOCS_MAX], smoothing negative or not finite, or
+ * min_tokens < 1; LDA_ERR_STATE with a pending delta (call lda_apply first).
+ * D = 0 succeeds with -1 / 0 / 0 everywhere.
+ * Device scratch is grow-only and kept by the context, and its bound depends
+ * on neither D nor N: the documents go through in chunks of at most
+ * max(1, 2^23 / Kp) documents, whose dense rows take at most 32 MiB; the
+ * (slab, topic) lists, at most 1024 (slab, 64-topic group) waves x 64 topics x
+ * n entries of 20 bytes (1.25 MiB x n: 12.5 MiB at n = 10, 160 MiB at
+ * n = 128), carried from chunk to chunk; and the 16 K n bytes of the result,
+ * which is all that is copied to the host.  Waits once for the context's
+ * stream. */
+#define LDA_TOPIC_DOCS_MAX 128
+lda_status lda_topic_top_docs(lda_ctx* ctx, int32_t n, double smoothing, int32_t min_tokens,
+                              int64_t* doc_ids /*[K*n]*/, int32_t* counts /*[K*n]*/, int32_t* lengths /*[K*n]*/);
+/* Test hook: lda_topic_top_docs cuts the documents into chunks of `docs`
+ * documents instead of 2^23 / Kp (0 = the default). */
+void lda_debug_topic_docs_chunk_docs(int64_t docs);
+
 /* Topic diagnostics: the integer statistics behind per-topic coherence,
  * document entropy, rank-1 documents, allocation ratio / count, exclusivity
  * and the distances from the uniform and corpus distributions, counted on the
@@ -835,8 +879,9 @@ void lda_debug_fail_host_alloc(int32_t nth);
  * lda_topic_word_stats, then lda_left_to_right (with its test hook
  * lda_debug_ltr_chunk_cells), then lda_topic_distances, lda_topic_nearest
  * and lda_topic_distance_slabs, then lda_word_cooccurrences (with its test
- * hook lda_debug_cooc_chunk_tokens) came later and only add symbols, so the
- * version stays 8. */
+ * hook lda_debug_cooc_chunk_tokens), then lda_topic_top_docs (with its test
+ * hook lda_debug_topic_docs_chunk_docs) came later and only add symbols, so
+ * the version stays 8. */
 #define LDA_ABI_VERSION 8
 const char* lda_version(void);
 int32_t lda_abi_version(void);

@@ -15,6 +15,7 @@
  *   getTopicProbabilities(topicSequence)          -> ldatm_get_topic_probabilities
  *   printDocumentTopics(File)                     -> ldatm_print_document_topics
  *   printTopWords(File, n, newLines)              -> ldatm_print_top_words
+ *   printTopicDocuments(File, max)                -> ldatm_print_topic_documents
  *   getInferencer().getSampledDistribution(...)   -> ldatm_infer
  *   the predict loop's similarity to every
  *   training document (Predictor.predict)        -> ldatm_score / ldatm_score_theta / ldatm_score_top
@@ -366,6 +367,45 @@ lda_status ldatm_print_top_words(ldatm* m, const char* path, int32_t num_words,
                                  int32_t using_new_lines);
 lda_status ldatm_top_words_text(ldatm* m, int32_t num_words, int32_t using_new_lines, char* buf,
                                 size_t cap, size_t* len);
+
+/* The documents in which each topic is heaviest, selected on the device
+ * (lda_topic_top_docs of lda_mi355x.h; the question Mallet's
+ * printTopicDocuments answers, by this library's definition: only documents
+ * with a token of the topic are candidates).
+ * ldatm_topic_top_docs: per topic k < K the n documents with n_dk > 0 and
+ * length >= min_tokens that have the largest weight
+ *     ((double) n_dk + smoothing) / ((double) L_d + (double) K * smoothing),
+ * weight descending, equal weights by ascending document id; GLOBAL document
+ * ids in doc_ids[K*n], n_dk in counts[K*n], L_d in lengths[K*n]; -1 / 0 / 0
+ * past a topic's last candidate.  Each shard selects among its own documents
+ * on its own device and stream; the local ids become global through the
+ * shards' document ranges and the host merges the shards' K x n lists by
+ * (weight descending, id ascending), each weight recomputed from (count,
+ * length) with the expression above.  A shard's list holds every one of its
+ * documents that belongs to the global best n, so the result does not depend
+ * on the number of shards, bit for bit.
+ * Errors, checked before any device work (a model without a GPU names its bad
+ * argument): LDA_ERR_INVALID_ARG for a NULL model, n outside
+ * [1, LDA_TOPIC_DOCS_MAX], smoothing negative or not finite, min_tokens < 1,
+ * or a NULL output.  Device scratch per shard as lda_topic_top_docs bounds
+ * it; the host holds shards x K x n entries.  Waits for the shards' streams.
+ * ldatm_print_topic_documents / ldatm_topic_documents_text: the selection
+ * with n = max as text, "#topic doc name proportion ...\n", then per topic
+ * and rank "<topic> <doc> <source|null-source> <weight>\n" (the name column
+ * and Java Double.toString of ldatm_print_document_topics); padded slots
+ * print nothing.  Same errors; buf / cap / len as the other *_text calls.
+ * ldatm_topic_documents_format: that text from the caller's K x n arrays
+ * (host only, no model and no device); names[num_names] gives the name column
+ * (NULL entry or an id >= num_names: "null-source"). */
+lda_status ldatm_topic_top_docs(ldatm* m, int32_t n, double smoothing, int32_t min_tokens,
+                                int64_t* doc_ids /*[K*n]*/, int32_t* counts /*[K*n]*/, int32_t* lengths /*[K*n]*/);
+lda_status ldatm_print_topic_documents(ldatm* m, const char* path, int32_t max, double smoothing,
+                                       int32_t min_tokens);
+lda_status ldatm_topic_documents_text(ldatm* m, int32_t max, double smoothing, int32_t min_tokens, char* buf,
+                                      size_t cap, size_t* len);
+lda_status ldatm_topic_documents_format(int32_t K, int32_t n, double smoothing, const int64_t* doc_ids,
+                                        const int32_t* counts, const int32_t* lengths, const char* const* names,
+                                        int64_t num_names, char* buf, size_t cap, size_t* len);
 
 /* Checkpoint / resume: the reference's save()/load() of its model
  * (src/cmu_ron/TrainAndPredict.java:179-200) as a native binary file holding

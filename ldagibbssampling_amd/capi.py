@@ -34,6 +34,8 @@ SCORE_METRICS = {"cosine": 0, "mse": 1}
 # LDA_TOP_WORDS_MAX / LDA_TOP_TOPICS_MAX of lda_mi355x.h
 TOP_WORDS_MAX = 64
 TOP_TOPICS_MAX = 64
+# LDA_TOPIC_DOCS_MAX of lda_mi355x.h
+TOPIC_DOCS_MAX = 128
 # LDA_DIAG_WORDS_MAX / LDA_DIAG_PROPS_MAX of lda_mi355x.h
 DIAG_WORDS_MAX = 64
 DIAG_PROPS_MAX = 8
@@ -179,6 +181,8 @@ SIGNATURES = {
     "lda_topic_word_stats": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "lda_word_cooccurrences": (C.c_int32, [_vp, C.c_int32, _vp, C.c_int32, C.c_int64, _vp, _vp, _vp, _vp]),
     "lda_debug_cooc_chunk_tokens": (None, [C.c_int64]),
+    "lda_topic_top_docs": (C.c_int32, [_vp, C.c_int32, C.c_double, C.c_int32, _vp, _vp, _vp]),
+    "lda_debug_topic_docs_chunk_docs": (None, [C.c_int64]),
     "lda_topic_distances": (C.c_int32, [_vp, _vp, C.c_int32, _vp]),
     "lda_topic_nearest": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
     "lda_topic_distance_slabs": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),

@@ -239,6 +239,17 @@ constexpr int64_t COOC_TOKENS = int64_t(1) << 23;
 constexpr int64_t COOC_DOCS = int64_t(1) << 20;
 constexpr int64_t COOC_BLOCKS_PER_CU = 4;
 int64_t g_cooc_tokens = 0;   // lda_debug_cooc_chunk_tokens (0: COOC_TOKENS)
+// lda_topic_top_docs: the documents go through in chunks of at most
+// TOPIC_DOCS_CELLS / Kp documents (32 MiB of dense int32 rows); a chunk's slab
+// pass as lda_top_words': at least TOPIC_DOCS_SLAB_DOCS documents per slab, at
+// most TOPIC_DOCS_WAVES (slab, topic group) waves, which bounds the lists at
+// TOPIC_DOCS_WAVES * 64 * n entries of 20 bytes (160 MiB at n = 128)
+constexpr int64_t TOPIC_DOCS_CELLS = int64_t(1) << 23;
+constexpr int64_t TOPIC_DOCS_SLAB_DOCS = 256;
+constexpr int64_t TOPIC_DOCS_WAVES = 1024;
+static_assert(LDA_TOPIC_DOCS_MAX == lda::TOPIC_DOCS_MAX, "the header states the kernels' limit");
+static_assert(TOPIC_DOCS_WAVES <= lda::TOPIC_DOCS_MAX_SLABS, "the merge holds every slab's head");
+int64_t g_topic_docs_chunk = 0;   // lda_debug_topic_docs_chunk_docs (0: TOPIC_DOCS_CELLS / Kp)
 // lda_top_words' slab pass: at least TOP_WORDS_SLAB_ROWS rows per slab (a
 // slab's list warms up over its first rows), at most TOP_WORDS_WAVES (slab,
 // topic group) waves, which bounds the slab lists at TOP_WORDS_WAVES * 64 * n
@@ -376,6 +387,13 @@ struct lda_ctx {
   unsigned long long* cc_out = nullptr;
   int64_t* cc_off = nullptr;
   size_t cc_cap[5] = {};
+  // lda_topic_top_docs: grow-only scratch -- a chunk's dense rows [Dc x Kp],
+  // the slab lists (weight bits, ids, counts: [slabs x Kp x n] each) and the
+  // result (ids [K n], then counts and lengths [2 K n])
+  int32_t *td_rows = nullptr, *td_cnts = nullptr, *td_out = nullptr;
+  unsigned long long* td_bits = nullptr;
+  int64_t *td_ids = nullptr, *td_out_ids = nullptr;
+  size_t td_cap[6] = {};
   // 16-bit rows of the snapshot (LDA_SAMPLER_DENSE)
   uint16_t* nw16 = nullptr;
   uint8_t* wide = nullptr;
@@ -531,6 +549,7 @@ struct lda_ctx {
                     (void*)ro_part, (void*)ro_sums, (void*)ro_mat, (void*)ro_vals, (void*)ro_ids,
                     (void*)dg_ids, (void*)dg_table, (void*)dg_out, (void*)dg_shares,
                     (void*)cc_moff, (void*)cc_mem, (void*)cc_words, (void*)cc_out, (void*)cc_off,
+                    (void*)td_rows, (void*)td_cnts, (void*)td_out, (void*)td_bits, (void*)td_ids, (void*)td_out_ids,
                     (void*)perm, (void*)items, (void*)warm.range_doc, (void*)steady.range_doc,
                     (void*)big.tab, (void*)big.tab_m1, (void*)big.F, (void*)big.pfx, (void*)big.scal})
       if (p) (void)hipFree(p);
@@ -2543,6 +2562,8 @@ hipError_t grow_bytes(void** ptr, size_t* cap, size_t bytes) {
   grow_bytes(reinterpret_cast<void**>(&(ptr)), &(c)->dg_cap[(slot)], (n) * sizeof(*(ptr)))
 #define cc_need(c, ptr, n, slot) \
   grow_bytes(reinterpret_cast<void**>(&(ptr)), &(c)->cc_cap[(slot)], (n) * sizeof(*(ptr)))
+#define td_need(c, ptr, n, slot) \
+  grow_bytes(reinterpret_cast<void**>(&(ptr)), &(c)->td_cap[(slot)], (n) * sizeof(*(ptr)))
 
 // the document arguments lda_score_docs takes, checked the same way
 lda_status check_doc_list(const lda_ctx* c, int64_t doc_begin, int64_t M, const int64_t* docs) {
@@ -2666,6 +2687,77 @@ lda_status lda_doc_top_topics(lda_ctx* c, int32_t m, int64_t doc_begin, int64_t 
   if (M == 0) return LDA_OK;
   if (!topics || !counts) return fail(LDA_ERR_INVALID_ARG, "null output");
   return doc_readout(c, m, doc_begin, M, docs, topics, counts);
+  });
+}
+
+void lda_debug_topic_docs_chunk_docs(int64_t docs) { g_topic_docs_chunk = docs > 0 ? docs : 0; }
+
+lda_status lda_topic_top_docs(lda_ctx* c, int32_t n, double smoothing, int32_t min_tokens, int64_t* doc_ids,
+                              int32_t* counts, int32_t* lengths) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (n < 1 || n > LDA_TOPIC_DOCS_MAX) return fail(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_TOPIC_DOCS_MAX]");
+  if (!(smoothing >= 0.0) || !std::isfinite(smoothing))
+    return fail(LDA_ERR_INVALID_ARG, "smoothing must be finite and not negative");
+  if (min_tokens < 1) return fail(LDA_ERR_INVALID_ARG, "min_tokens must be at least 1");
+  if (!doc_ids || !counts || !lengths) return fail(LDA_ERR_INVALID_ARG, "null output");
+  if (c->pending) return fail(LDA_ERR_STATE, "top documents with a pending delta: call lda_apply first");
+  const size_t cells = (size_t)c->K * (size_t)n;
+  if (c->D == 0) {
+    std::fill(doc_ids, doc_ids + cells, (int64_t)-1);
+    std::fill(counts, counts + cells, 0);
+    std::fill(lengths, lengths + cells, 0);
+    return LDA_OK;
+  }
+  const int64_t G = c->Kp / 64;
+  const int64_t chunk = g_topic_docs_chunk > 0 ? g_topic_docs_chunk : std::max<int64_t>(1, TOPIC_DOCS_CELLS / c->Kp);
+  const int64_t Dc = std::min<int64_t>(c->D, chunk);
+  // the slabs of the first chunk; every later chunk is cut the same way
+  int64_t slabs = std::min<int64_t>((Dc + TOPIC_DOCS_SLAB_DOCS - 1) / TOPIC_DOCS_SLAB_DOCS,
+                                    std::max<int64_t>(1, TOPIC_DOCS_WAVES / G));
+  const int64_t slab_docs = (Dc + slabs - 1) / slabs;
+  slabs = (Dc + slab_docs - 1) / slab_docs;
+  const size_t entries = (size_t)(slabs * c->Kp) * (size_t)n;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(td_need(c, c->td_rows, (size_t)(Dc * c->Kp), 0));
+  HIP_TRY(td_need(c, c->td_bits, entries, 1));
+  HIP_TRY(td_need(c, c->td_ids, entries, 2));
+  HIP_TRY(td_need(c, c->td_cnts, entries, 3));
+  HIP_TRY(td_need(c, c->td_out_ids, cells, 4));
+  HIP_TRY(td_need(c, c->td_out, 2 * cells, 5));
+  lda::TopicDocsArgs a{};
+  a.z = c->z;
+  a.doc_off = c->doc_off;
+  a.slab_docs = slab_docs;
+  a.K = c->K;
+  a.Kp = c->Kp;
+  a.n = n;
+  a.min_tokens = min_tokens;
+  a.slabs = (int32_t)slabs;
+  a.smoothing = smoothing;
+  a.Ks = (double)c->K * smoothing;
+  a.rows = c->td_rows;
+  a.bits = c->td_bits;
+  a.ids = c->td_ids;
+  a.cnts = c->td_cnts;
+  a.out_ids = c->td_out_ids;
+  a.out_counts = c->td_out;
+  a.out_lengths = c->td_out + cells;
+  const int64_t wave_blocks = (int64_t)c->cus * 8;
+  // the stream orders the chunks: a chunk's rows are read before the next
+  // chunk's count pass overwrites them
+  for (int64_t d0 = 0; d0 < c->D; d0 += Dc) {
+    a.doc_begin = d0;
+    a.M = std::min<int64_t>(Dc, c->D - d0);
+    a.first = d0 == 0;
+    HIP_TRY(lda::launch_topic_docs_chunk(a, (int)std::min<int64_t>((a.M + 3) / 4, wave_blocks), c->stream));
+  }
+  HIP_TRY(lda::launch_topic_docs_merge(a, c->stream));
+  HIP_TRY(hipMemcpyAsync(doc_ids, a.out_ids, sizeof(int64_t) * cells, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(counts, a.out_counts, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(lengths, a.out_lengths, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LDA_OK;
   });
 }
 

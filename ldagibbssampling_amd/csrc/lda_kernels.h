@@ -269,6 +269,36 @@ struct DocReadoutArgs {
 };
 hipError_t launch_doc_counts(const DocReadoutArgs& a, int blocks, hipStream_t st);
 hipError_t launch_doc_top_topics(const DocReadoutArgs& a, int blocks, hipStream_t st);
+// lda_topic_top_docs: the shard's documents go through in chunks.  Per chunk,
+// k_topic_docs_count writes the chunk's dense rows [M * Kp] and
+// k_topic_docs_slab folds them into the (slab, topic) lists: the descending
+// best n of every topic among the documents slab s has seen so far, as
+// weight bits / ids / counts at [((slab * G + group) * n + i) * 64 + lane]
+// (G = Kp / 64; bits 0 = an empty slot).  Slab s of a chunk is its documents
+// [s * slab_docs, min(M, (s + 1) * slab_docs)); slabs and slab_docs are those
+// of the first chunk (first != 0: the lists start empty), a shorter last
+// chunk leaves its trailing slabs untouched.  k_topic_docs_merge then merges
+// a topic's slab lists into out_* [K * n].  slabs <= TOPIC_DOCS_MAX_SLABS.
+constexpr int TOPIC_DOCS_MAX = 128;
+constexpr int TOPIC_DOCS_MAX_SLABS = 1024;
+struct TopicDocsArgs {
+  const int32_t* z;
+  const int64_t* doc_off;
+  int64_t doc_begin, M;          // the chunk: documents [doc_begin, doc_begin + M) of the shard
+  int64_t slab_docs;
+  int32_t K, Kp, n, min_tokens;
+  int32_t slabs, first;
+  double smoothing, Ks;          // Ks = (double) K * smoothing
+  int32_t* rows;                 // [M * Kp]
+  unsigned long long* bits;      // [slabs * Kp * n]
+  int64_t* ids;                  // [slabs * Kp * n]
+  int32_t* cnts;                 // [slabs * Kp * n]
+  int64_t* out_ids;              // [K * n]
+  int32_t* out_counts;           // [K * n]
+  int32_t* out_lengths;          // [K * n]
+};
+hipError_t launch_topic_docs_chunk(const TopicDocsArgs& a, int blocks, hipStream_t st);
+hipError_t launch_topic_docs_merge(const TopicDocsArgs& a, hipStream_t st);
 // lda_topic_codocuments, the co-document count (k_codoc): grid (document
 // slabs, topic groups); a block keeps the packed triangles of its
 // group_topics topics in LDS, a wave takes a document, marks the listed words

@@ -5305,4 +5305,182 @@ hipError_t launch_cooc(const CoocArgs& a, int slabs, hipStream_t st) {
   return hipGetLastError();
 }
 
+// lda_topic_top_docs, count pass: the dense nd rows of the chunk's documents
+// [doc_begin, doc_begin + M), k_doc_counts' per-wave histogram with a row
+// stride of Kp (padded topics 0), so that the slab pass loads a 64-topic
+// segment of a row as one coalesced 256 bytes.  Each lane writes and clears
+// the cells it read.
+__global__ __launch_bounds__(256) void k_topic_docs_count(const TopicDocsArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int32_t h[];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  int32_t* hist = h + wid * a.Kp;
+  for (int i = lane; i < a.Kp; i += 64) hist[i] = 0;
+  wave_lds_fence();
+  const int32_t* __restrict__ z = a.z;
+  for (int64_t j = (int64_t)blockIdx.x * 4 + wid; j < a.M; j += (int64_t)gridDim.x * 4) {
+    const int64_t d = a.doc_begin + j;
+    for (int64_t i = a.doc_off[d] + lane; i < a.doc_off[d + 1]; i += 64) atomicAdd(&hist[z[i]], 1);
+    wave_lds_fence();
+    int32_t* __restrict__ row = a.rows + j * a.Kp;
+    for (int k = lane; k < a.Kp; k += 64) {
+      row[k] = hist[k];
+      hist[k] = 0;
+    }
+    wave_lds_fence();
+  }
+}
+
+// lda_topic_top_docs, slab pass: one wave per (slab of the chunk's documents,
+// group of 64 topics), lane l owning topic group * 64 + l, as
+// k_top_words_slab cuts the word rows.  The lane's best n documents are a
+// descending list: the bits of the weights in its own LDS column
+// list[i * 64 + lane] (positive doubles order as unsigned integers; 0 = an
+// empty slot), the ids and counts beside them in the context's scratch
+// (ids / cnts[i * 64], touched by this lane alone).  Documents arrive in
+// ascending id -- within the slab and from chunk to chunk, since slab s of a
+// chunk continues slab s's list of the chunk before (first == 0: the bits come
+// back from the scratch) -- so the strict compare keeps the smaller id first
+// among equal weights and drops an equal weight at a full list's end.  The
+// smallest kept weight (thr) stays in a register: a document that does not
+// beat it costs one division and one compare.  len, the filled slots, spares
+// a list that is not yet full the shift through its empty tail.  No atomics;
+// the list is a function of the documents the slab has seen.
+__global__ __launch_bounds__(64) void k_topic_docs_slab(const TopicDocsArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long td_list[];   // [n][64]
+  const int lane = threadIdx.x, n = a.n;
+  const int s = blockIdx.x, g = blockIdx.y, G = a.Kp >> 6;
+  const int64_t j0 = (int64_t)s * a.slab_docs, j1 = min(a.M, j0 + a.slab_docs);
+  if (j0 >= j1) return;   // a short last chunk: the slab's list stays as it is
+  const size_t base = ((size_t)s * G + g) * n * 64 + lane;
+  unsigned long long* gb = a.bits + base;
+  int64_t* gi = a.ids + base;
+  int32_t* gc = a.cnts + base;
+  int len = 0;
+  for (int i = 0; i < n; ++i) {
+    const unsigned long long b = a.first ? 0ull : gb[(size_t)i * 64];
+    td_list[i * 64 + lane] = b;
+    len += b != 0;
+  }
+  unsigned long long thr = td_list[(n - 1) * 64 + lane];
+  const int32_t* __restrict__ col = a.rows + (size_t)g * 64 + lane;
+  const int64_t* __restrict__ off = a.doc_off + a.doc_begin;
+  for (int64_t j = j0; j < j1; j += 4) {
+    int32_t c[4];
+    int64_t L[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const bool in = j + u < j1;
+      c[u] = in ? col[(size_t)(j + u) * a.Kp] : 0;
+      L[u] = in ? off[j + u + 1] - off[j + u] : 0;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (c[u] <= 0 || L[u] < a.min_tokens) continue;
+      const unsigned long long key =
+          (unsigned long long)__double_as_longlong(((double)c[u] + a.smoothing) / ((double)L[u] + a.Ks));
+      if (key > thr) {
+        int i = min(len, n - 1);
+        while (i > 0) {
+          const unsigned long long prev = td_list[(i - 1) * 64 + lane];
+          if (prev >= key) break;
+          td_list[i * 64 + lane] = prev;
+          gi[(size_t)i * 64] = gi[(size_t)(i - 1) * 64];
+          gc[(size_t)i * 64] = gc[(size_t)(i - 1) * 64];
+          --i;
+        }
+        td_list[i * 64 + lane] = key;
+        gi[(size_t)i * 64] = a.doc_begin + j + u;
+        gc[(size_t)i * 64] = c[u];
+        len = min(len + 1, n);
+        thr = td_list[(n - 1) * 64 + lane];
+      }
+    }
+  }
+  for (int i = 0; i < n; ++i) gb[(size_t)i * 64] = td_list[i * 64 + lane];
+}
+
+// lda_topic_top_docs, merge pass: one wave per topic k < K merges the topic's
+// slab lists as k_top_words_merge does, lane l holding the heads of slabs l,
+// l + 64, ...  The arg-max is over (weight bits, then smaller id): weights
+// repeat across documents, the pair does not, so the winner names its slab,
+// whose owner writes the slot and steps the list.  An exhausted merge fills
+// id -1, count 0, length 0.
+__global__ __launch_bounds__(64) void k_topic_docs_merge(const TopicDocsArgs a) {
+  __shared__ unsigned long long head[TOPIC_DOCS_MAX_SLABS];
+  __shared__ long long hid[TOPIC_DOCS_MAX_SLABS];
+  __shared__ int32_t ptr[TOPIC_DOCS_MAX_SLABS];
+  const int lane = threadIdx.x, n = a.n, k = blockIdx.x, g = k >> 6, kl = k & 63, G = a.Kp >> 6;
+  auto at = [&](int s, int i) { return (((size_t)s * G + g) * n + i) * 64 + kl; };
+  for (int s = lane; s < a.slabs; s += 64) {
+    const unsigned long long b = a.bits[at(s, 0)];
+    head[s] = b;
+    hid[s] = b ? a.ids[at(s, 0)] : INT64_MAX;
+    ptr[s] = 0;
+  }
+  for (int i = 0; i < n; ++i) {
+    unsigned long long best = 0;
+    long long bid = INT64_MAX;
+    int bs = -1;
+    for (int s = lane; s < a.slabs; s += 64) {
+      const unsigned long long hb = head[s];
+      const long long id = hid[s];
+      if (hb > best || (hb == best && id < bid)) {
+        best = hb;
+        bid = id;
+        bs = s;
+      }
+    }
+    unsigned long long wb = best;
+    long long wi = bid;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const uint32_t bh = (uint32_t)__shfl_xor((int)(wb >> 32), o), bl = (uint32_t)__shfl_xor((int)(uint32_t)wb, o);
+      const uint32_t ih = (uint32_t)__shfl_xor((int)((unsigned long long)wi >> 32), o);
+      const uint32_t il = (uint32_t)__shfl_xor((int)(uint32_t)wi, o);
+      const unsigned long long ob = ((unsigned long long)bh << 32) | bl;
+      const long long oi = (long long)(((unsigned long long)ih << 32) | il);
+      if (ob > wb || (ob == wb && oi < wi)) {
+        wb = ob;
+        wi = oi;
+      }
+    }
+    const size_t o = (size_t)k * n + i;
+    if (wb == 0) {
+      if (lane == 0) {
+        a.out_ids[o] = -1;
+        a.out_counts[o] = 0;
+        a.out_lengths[o] = 0;
+      }
+    } else if (best == wb && bid == wi) {   // this lane owns the winner's slab
+      int p = ptr[bs];
+      a.out_ids[o] = wi;
+      a.out_counts[o] = a.cnts[at(bs, p)];
+      a.out_lengths[o] = (int32_t)(a.doc_off[wi + 1] - a.doc_off[wi]);
+      ptr[bs] = ++p;
+      const unsigned long long nb = p < n ? a.bits[at(bs, p)] : 0ull;
+      head[bs] = nb;
+      hid[bs] = nb ? a.ids[at(bs, p)] : INT64_MAX;
+    }
+  }
+}
+
+hipError_t launch_topic_docs_chunk(const TopicDocsArgs& a, int blocks, hipStream_t st) {
+  if (a.n < 1 || a.n > TOPIC_DOCS_MAX || a.slabs < 1 || a.slabs > TOPIC_DOCS_MAX_SLABS || a.M < 1 || blocks < 1 ||
+      a.slab_docs < 1 || (a.first && (int64_t)a.slabs * a.slab_docs < a.M))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_topic_docs_count, dim3(blocks), dim3(256), 4 * (size_t)a.Kp * sizeof(int32_t), st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  // 512 n bytes of LDS per one-wave block: 64 KiB at n = 128, the default limit
+  hipLaunchKernelGGL(k_topic_docs_slab, dim3(a.slabs, a.Kp / 64), dim3(64),
+                     (size_t)a.n * 64 * sizeof(unsigned long long), st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_topic_docs_merge(const TopicDocsArgs& a, hipStream_t st) {
+  if (a.n < 1 || a.n > TOPIC_DOCS_MAX || a.slabs < 1 || a.slabs > TOPIC_DOCS_MAX_SLABS) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_topic_docs_merge, dim3(a.K), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
 }  // namespace lda

@@ -1047,6 +1047,92 @@ void ParallelTopicModel::docTopTopics(int32_t mtop, int64_t M, const int64_t* do
 void ParallelTopicModel::docCounts(int64_t M, const int64_t* docs, int32_t* nd) { docReadout(0, M, docs, nd, nullptr); }
 
 namespace {
+// lda_topic_top_docs' argument checks, before any shard is built
+void checkTopicDocs(int32_t n, double smoothing, int32_t min_tokens) {
+  if (n < 1 || n > LDA_TOPIC_DOCS_MAX) raise(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_TOPIC_DOCS_MAX]");
+  if (!(smoothing >= 0.0) || !std::isfinite(smoothing))
+    raise(LDA_ERR_INVALID_ARG, "smoothing must be finite and not negative");
+  if (min_tokens < 1) raise(LDA_ERR_INVALID_ARG, "min_tokens must be at least 1");
+}
+}  // namespace
+
+double topicDocWeight(int32_t K, double smoothing, int32_t count, int32_t length) {
+  const double Ks = (double)K * smoothing;
+  return ((double)count + smoothing) / ((double)length + Ks);
+}
+
+void ParallelTopicModel::topicTopDocs(int32_t n, double smoothing, int32_t min_tokens, int64_t* doc_ids,
+                                      int32_t* counts, int32_t* lengths) {
+  checkTopicDocs(n, smoothing, min_tokens);
+  if (!doc_ids || !counts || !lengths) raise(LDA_ERR_INVALID_ARG, "null output");
+  ensureShards();
+  const size_t G = shards_->ctx.size(), cells = (size_t)K_ * (size_t)n;
+  if (G == 1) {
+    check(lda_topic_top_docs(shards_->ctx[0], n, smoothing, min_tokens, doc_ids, counts, lengths),
+          "lda_topic_top_docs");
+    return;
+  }
+  // every shard's K x n lists (local ids), then per topic the best n of the
+  // shards' candidates by (weight descending, global id ascending), the
+  // weight recomputed from (count, length) with the device's expression
+  std::vector<int64_t> ids(G * cells);
+  std::vector<int32_t> cnt(G * cells), len(G * cells);
+  for (size_t g = 0; g < G; ++g)
+    check(lda_topic_top_docs(shards_->ctx[g], n, smoothing, min_tokens, ids.data() + g * cells,
+                             cnt.data() + g * cells, len.data() + g * cells),
+          "lda_topic_top_docs");
+  struct Cand {
+    double w;
+    int64_t id;
+    int32_t count, length;
+  };
+  std::vector<Cand> cand;
+  for (int32_t k = 0; k < K_; ++k) {
+    cand.clear();
+    for (size_t g = 0; g < G; ++g)
+      for (int32_t i = 0; i < n; ++i) {
+        const size_t at = g * cells + (size_t)k * n + i;
+        if (ids[at] < 0) break;
+        cand.push_back({topicDocWeight(K_, smoothing, cnt[at], len[at]), ids[at] + shards_->doc_begin[g], cnt[at],
+                        len[at]});
+      }
+    std::sort(cand.begin(), cand.end(),
+              [](const Cand& a, const Cand& b) { return a.w > b.w || (a.w == b.w && a.id < b.id); });
+    for (int32_t i = 0; i < n; ++i) {
+      const size_t o = (size_t)k * n + i;
+      const bool has = (size_t)i < cand.size();
+      doc_ids[o] = has ? cand[(size_t)i].id : -1;
+      counts[o] = has ? cand[(size_t)i].count : 0;
+      lengths[o] = has ? cand[(size_t)i].length : 0;
+    }
+  }
+}
+
+std::string topicDocumentsFormat(int32_t K, int32_t n, double smoothing, const int64_t* doc_ids, const int32_t* counts,
+                                 const int32_t* lengths, const std::function<std::string(int64_t)>& name) {
+  std::string out = "#topic doc name proportion ...\n";
+  for (int32_t k = 0; k < K; ++k)
+    for (int32_t i = 0; i < n; ++i) {
+      const size_t at = (size_t)k * n + i;
+      if (doc_ids[at] < 0) break;
+      out += std::to_string(k) + " " + std::to_string(doc_ids[at]) + " " + name(doc_ids[at]) + " " +
+             java_double(topicDocWeight(K, smoothing, counts[at], lengths[at])) + "\n";
+    }
+  return out;
+}
+
+std::string ParallelTopicModel::topicDocuments(int32_t max, double smoothing, int32_t min_tokens) {
+  checkTopicDocs(max, smoothing, min_tokens);
+  const size_t cells = (size_t)K_ * (size_t)max;
+  std::vector<int64_t> ids(cells);
+  std::vector<int32_t> cnt(cells), len(cells);
+  topicTopDocs(max, smoothing, min_tokens, ids.data(), cnt.data(), len.data());
+  return topicDocumentsFormat(K_, max, smoothing, ids.data(), cnt.data(), len.data(), [&](int64_t d) {
+    return has_source_[(size_t)d] ? sources_[(size_t)d] : std::string("null-source");
+  });
+}
+
+namespace {
 // Mallet's TopicModelDiagnostics thresholds (its DEFAULT_DOC_PROPORTIONS)
 constexpr double DIAG_PROPS[LDATM_DIAG_PROPS] = {0.01, 0.02, 0.05, 0.1, 0.2, 0.3, 0.5};
 
@@ -2189,6 +2275,45 @@ lda_status ldatm_print_top_words(ldatm* m, const char* path, int32_t num_words, 
   std::string s;
   lda_status st = guard([&] { s = m->model.displayTopWords(num_words, using_new_lines != 0); });
   return st ? st : write_file(path, s);
+}
+
+lda_status ldatm_topic_top_docs(ldatm* m, int32_t n, double smoothing, int32_t min_tokens, int64_t* doc_ids,
+                                int32_t* counts, int32_t* lengths) {
+  TM_CHECK(m);
+  return guard([&] { m->model.topicTopDocs(n, smoothing, min_tokens, doc_ids, counts, lengths); });
+}
+
+lda_status ldatm_topic_documents_text(ldatm* m, int32_t max, double smoothing, int32_t min_tokens, char* buf,
+                                      size_t cap, size_t* len) {
+  TM_CHECK(m);
+  std::string s;
+  lda_status st = guard([&] { s = m->model.topicDocuments(max, smoothing, min_tokens); });
+  return st ? st : copy_text(s, buf, cap, len);
+}
+
+lda_status ldatm_print_topic_documents(ldatm* m, const char* path, int32_t max, double smoothing,
+                                       int32_t min_tokens) {
+  TM_CHECK(m);
+  std::string s;
+  lda_status st = guard([&] { s = m->model.topicDocuments(max, smoothing, min_tokens); });
+  return st ? st : write_file(path, s);
+}
+
+lda_status ldatm_topic_documents_format(int32_t K, int32_t n, double smoothing, const int64_t* doc_ids,
+                                        const int32_t* counts, const int32_t* lengths, const char* const* names,
+                                        int64_t num_names, char* buf, size_t cap, size_t* len) {
+  if (K < 1 || n < 1 || !(smoothing >= 0.0) || !std::isfinite(smoothing) || !doc_ids || !counts || !lengths ||
+      num_names < 0 || (num_names > 0 && !names)) {
+    g_tm_error = "bad argument";
+    return LDA_ERR_INVALID_ARG;
+  }
+  std::string s;
+  lda_status st = guard([&] {
+    s = lda_host::topicDocumentsFormat(K, n, smoothing, doc_ids, counts, lengths, [&](int64_t d) {
+      return d < num_names && names[d] ? std::string(names[d]) : std::string("null-source");
+    });
+  });
+  return st ? st : copy_text(s, buf, cap, len);
 }
 
 lda_status ldatm_save(ldatm* m, const char* path) {

@@ -7,6 +7,7 @@
 // one context per GPU shard, RCCL all-reduce of the int32 delta between them).
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <string>
 #include <utility>
@@ -39,6 +40,13 @@ void diagnosticsFinish(int32_t K, int32_t V, int32_t n, double beta, const int32
 // sums [K] over the kept pairs and their number pairs [K]
 void coherenceFinish(int32_t K, int32_t n, int32_t measure, double epsilon, const int64_t* cooc, int64_t units,
                      double* sums, int64_t* pairs);
+
+// lda_topic_top_docs' weight, ((double) count + smoothing) / ((double) length
+// + (double) K * smoothing), and printTopicDocuments' text from K x n lists
+// (host only, no device; ldatm_topic_documents_format of lda_topic_model.h)
+double topicDocWeight(int32_t K, double smoothing, int32_t count, int32_t length);
+std::string topicDocumentsFormat(int32_t K, int32_t n, double smoothing, const int64_t* doc_ids, const int32_t* counts,
+                                 const int32_t* lengths, const std::function<std::string(int64_t)>& name);
 
 class ParallelTopicModel {
  public:
@@ -122,6 +130,13 @@ class ParallelTopicModel {
   // scattered back into the caller's order.  topics / counts [M*mtop]; nd [M*K]
   void docTopTopics(int32_t mtop, int64_t M, const int64_t* docs, int32_t* topics, int32_t* counts);
   void docCounts(int64_t M, const int64_t* docs, int32_t* nd);
+  // lda_topic_top_docs on every shard, the local ids made
+  // global, and the shards' lists merged per topic by (weight descending, id
+  // ascending) with the weight recomputed from (count, length): doc_ids /
+  // counts / lengths [K*n], -1 / 0 / 0 past a topic's last candidate.  The
+  // arguments are checked before any shard is built.
+  void topicTopDocs(int32_t n, double smoothing, int32_t min_tokens, int64_t* doc_ids, int32_t* counts,
+                    int32_t* lengths);
 
   // ---- topic diagnostics --------------------------------
   // lda_topic_codocuments on every shard with the caller's lists, summed in
@@ -160,6 +175,8 @@ class ParallelTopicModel {
   // ---- outputs -------------------------------------------------------
   std::string documentTopics(double threshold, int32_t max);
   std::string displayTopWords(int32_t num_words, bool using_new_lines);
+  // topicTopDocs(max) as text: "topic doc name weight" per topic and rank
+  std::string topicDocuments(int32_t max, double smoothing, int32_t min_tokens);
 
   // ---- checkpoint / resume (the reference's save()/load(),
   //      src/cmu_ron/TrainAndPredict.java:179-200, as a native format) ----

@@ -433,6 +433,23 @@ class GibbsSampler:
                                           nd.ctypes.data), "lda_doc_counts")
         return nd
 
+    def topic_top_docs(self, n: int, smoothing: float = 0.0, min_tokens: int = 1):
+        """lda_topic_top_docs: per topic the n documents of this shard with at
+        least one token of the topic and at least min_tokens tokens that have
+        the largest weight (n_dk + smoothing) / (L_d + K smoothing), equal
+        weights by ascending document id, selected on the device from z.
+        Returns (docs[K, n] int64, counts[K, n] int32, lengths[K, n] int32);
+        slots past a topic's last candidate hold -1 / 0 / 0."""
+        n = int(n)
+        if not 1 <= n <= capi.TOPIC_DOCS_MAX:
+            raise ValueError(f"n must be in [1, {capi.TOPIC_DOCS_MAX}]")
+        docs = np.zeros((self.K, n), dtype=np.int64)
+        cnt = np.zeros((self.K, n), dtype=np.int32)
+        lens = np.zeros((self.K, n), dtype=np.int32)
+        capi.check(self._L.lda_topic_top_docs(self._h, n, float(smoothing), int(min_tokens), docs.ctypes.data,
+                                              cnt.ctypes.data, lens.ctypes.data), "lda_topic_top_docs")
+        return docs, cnt, lens
+
     def _word_lists(self, word_ids):
         """(ids[K, n] int32, n) of K word lists, -1 = an empty slot."""
         ids = np.ascontiguousarray(word_ids, dtype=np.int32)

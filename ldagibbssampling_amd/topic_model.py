@@ -91,6 +91,11 @@ TM_SIGNATURES = {
                                           C.POINTER(C.c_size_t)]),
     "ldatm_print_top_words": (_i32, [_vp, C.c_char_p, _i32, _i32]),
     "ldatm_top_words_text": (_i32, [_vp, _i32, _i32, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ldatm_topic_top_docs": (_i32, [_vp, _i32, C.c_double, _i32, _vp, _vp, _vp]),
+    "ldatm_print_topic_documents": (_i32, [_vp, C.c_char_p, _i32, C.c_double, _i32]),
+    "ldatm_topic_documents_text": (_i32, [_vp, _i32, C.c_double, _i32, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ldatm_topic_documents_format": (_i32, [_i32, _i32, C.c_double, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_size_t,
+                                            C.POINTER(C.c_size_t)]),
     "ldatm_save": (_i32, [_vp, C.c_char_p]),
     "ldatm_load": (_i32, [C.POINTER(_vp), C.c_char_p]),
     "ldatm_infer": (_i32, [_vp, C.c_int64, _i64p, _vp, _i32, _i32, _i32, C.c_uint64, _f64p]),
@@ -139,6 +144,38 @@ def format_double(x: float, style: int = 0) -> str:
     """Java Double.toString (style 0) / Mallet's 5-digit NumberFormat (style 1)."""
     buf = C.create_string_buffer(128)
     _check(load_tm().ldatm_format_double(float(x), int(style), buf, 128), "ldatm_format_double")
+    return buf.value.decode()
+
+
+def topic_document_weights(K: int, smoothing: float, docs, counts, lengths) -> np.ndarray:
+    """lda_topic_top_docs' weight (n_dk + smoothing) / (L_d + K smoothing) of
+    every slot, float64, with K smoothing formed first; NaN where the id is -1."""
+    docs = np.asarray(docs)
+    ks = float(K) * float(smoothing)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        w = (np.asarray(counts, np.float64) + float(smoothing)) / (np.asarray(lengths, np.float64) + ks)
+    return np.where(docs >= 0, w, np.nan)
+
+
+def format_topic_documents(docs, counts, lengths, smoothing: float = 10.0, names=None) -> str:
+    """ldatm_topic_documents_format (host only, no device): printTopicDocuments'
+    text from [K, n] arrays as topicDocuments returns them; names[d] is
+    document d's name column (None, or no entry: "null-source")."""
+    ids = np.ascontiguousarray(docs, np.int64)
+    cnt = np.ascontiguousarray(counts, np.int32)
+    lens = np.ascontiguousarray(lengths, np.int32)
+    if ids.ndim != 2 or cnt.shape != ids.shape or lens.shape != ids.shape:
+        raise ValueError("docs, counts and lengths must be [K, n] arrays of one shape")
+    K, n = ids.shape
+    names = list(names or [])
+    arr = (C.c_char_p * max(len(names), 1))(*[None if s is None else str(s).encode() for s in names])
+    L = load_tm()
+    size = C.c_size_t()
+    args = (K, n, float(smoothing), ids.ctypes.data, cnt.ctypes.data, lens.ctypes.data,
+            C.cast(arr, C.c_void_p), len(names))
+    _check(L.ldatm_topic_documents_format(*args, None, 0, C.byref(size)), "ldatm_topic_documents_format")
+    buf = C.create_string_buffer(size.value + 1)
+    _check(L.ldatm_topic_documents_format(*args, buf, size.value + 1, C.byref(size)), "ldatm_topic_documents_format")
     return buf.value.decode()
 
 
@@ -453,6 +490,31 @@ class ParallelTopicModel:
                                             topics.ctypes.data, cnt.ctypes.data), "docTopTopics")
         return topics, cnt
 
+    # ------------------------------- top documents per topic
+    def topicDocuments(self, n: int, smoothing: float = 10.0, minTokens: int = 1):
+        """ldatm_topic_top_docs: per topic the n documents with a token of the
+        topic and at least minTokens tokens that have the largest weight
+        (n_dk + smoothing) / (L_d + K smoothing), equal weights by ascending
+        document id, selected on the device.  Returns (docs[K, n] int64 global
+        ids, weights[K, n] float64, counts[K, n] int32, lengths[K, n] int32);
+        -1 / NaN / 0 / 0 past a topic's last candidate.  The weights are
+        recomputed here from the counts and lengths."""
+        n = int(n)
+        if not 1 <= n <= capi.TOPIC_DOCS_MAX:
+            raise ValueError(f"n must be in [1, {capi.TOPIC_DOCS_MAX}]")
+        K = self.numTopics
+        docs = np.zeros((K, n), np.int64)
+        cnt = np.zeros((K, n), np.int32)
+        lens = np.zeros((K, n), np.int32)
+        _check(self._L.ldatm_topic_top_docs(self._h, n, float(smoothing), int(minTokens), docs.ctypes.data,
+                                            cnt.ctypes.data, lens.ctypes.data), "topicDocuments")
+        return docs, topic_document_weights(K, smoothing, docs, cnt, lens), cnt, lens
+
+    def getTopicDocuments(self, n: int = 100, smoothing: float = 10.0, minTokens: int = 1) -> list:
+        """Per topic a list of (doc, weight), at most n long, heaviest first."""
+        docs, w, _, _ = self.topicDocuments(n, smoothing, minTokens)
+        return [[(int(d), float(x)) for d, x in zip(docs[k], w[k]) if d >= 0] for k in range(self.numTopics)]
+
     # ------------------------------- topic distances (DESIGN 9g)
     def _other_model(self, other):
         """(native handle or None, K2) of the other side of a topic
@@ -657,6 +719,15 @@ class ParallelTopicModel:
     def printTopWords(self, path, numWords: int, usingNewLines: bool = False):
         _check(self._L.ldatm_print_top_words(self._h, os.fsencode(path), int(numWords),
                                              int(bool(usingNewLines))), "printTopWords")
+
+    def topicDocumentsText(self, max: int = 100, smoothing: float = 10.0, minTokens: int = 1) -> str:
+        """printTopicDocuments' text: "#topic doc name proportion ...", then
+        per topic and rank "topic doc name weight"."""
+        return self._text(self._L.ldatm_topic_documents_text, int(max), float(smoothing), int(minTokens))
+
+    def printTopicDocuments(self, path, max: int = 100, smoothing: float = 10.0, minTokens: int = 1):
+        _check(self._L.ldatm_print_topic_documents(self._h, os.fsencode(path), int(max), float(smoothing),
+                                                   int(minTokens)), "printTopicDocuments")
 
     # ------------------------------------------------ checkpoint / resume
     def save(self, path):
