@@ -597,6 +597,81 @@ lda_status lda_topic_top_docs(lda_ctx* ctx, int32_t n, double smoothing, int32_t
  * documents instead of 2^23 / Kp (0 = the default). */
 void lda_debug_topic_docs_chunk_docs(int64_t docs);
 
+/* lda_topic_phrases: the most frequent same-topic token runs of every topic of
+ * THIS shard -- the question Mallet's --xml-topic-phrase-report
+ * (topicPhraseXMLReport) answers -- counted on the device from the shard's
+ * words and current z.
+ * A RUN is a maximal range of consecutive tokens [s, e) inside one document
+ * with z[s] = ... = z[e-1] = k: it extends neither left nor right and never
+ * crosses a document's end.  Its PHRASE is (k, words[s..e)).  A run qualifies
+ * if min_len <= e - s <= max_len, 2 <= min_len <= max_len <=
+ * LDA_PHRASE_LEN_MAX.  A run longer than max_len is not cut into pieces: it
+ * counts toward *skipped_long and nothing else; a run shorter than min_len
+ * counts toward nothing.  count(k, phrase) is the number of qualifying runs
+ * with that topic and exactly that word sequence.
+ * Per topic the phrases are ordered by count descending, equal counts by word
+ * id sequence lexicographically ascending, a proper prefix before its
+ * extension: a strict total order on content alone, so a topic's best n are
+ * one set however the work is cut into passes, and a call repeats bit for bit.
+ * For each topic k < K the first n phrases with count >= min_count go to
+ * phrase_words[(k*n + i) * max_len + j] (-1 past the phrase's length),
+ * lengths[k*n + i], counts[k*n + i] and first[k*n + i], the smallest
+ * shard-local token index at which a qualifying run of the phrase starts;
+ * empty slots hold words -1, length 0, count 0, first -1.  topic_runs[k] is
+ * the topic's qualifying runs, topic_distinct[k] its distinct phrases before
+ * min_count.
+ * This is this library's definition, not Mallet's.  As recalled (Mallet is
+ * not vendored; nothing is tested against it), Mallet 2.0.7's loop never
+ * counts a run that reaches a document's last token and does not let the token
+ * that closes a phrase start the next one; both are accidents of its state
+ * machine and neither holds here.
+ * The counts live in a device hash table (open addressing, linear probing,
+ * one 64-bit key topic:12 | length-1:5 | start:47 and one 32-bit count per
+ * slot; the key refers to the read-only words, so an insert is one
+ * compare-and-swap, one add and one minimum, without a lock or a wait; every
+ * probe sequence ends after `slots` steps).  The table has the smallest power
+ * of two of slots >= 2 * (N / min_len), at most 2^28 (3 GiB, plus 1 GiB for
+ * the selection); beyond that the runs are cut by their hash into passes, each
+ * filling at most half the table from a count made beforehand, each followed
+ * by a selection whose per-topic list carries over to the next; a phrase
+ * lives in exactly one pass, so this is exact.
+ * lda_phrase_counts: the exact count of each of Q given (topic, word
+ * sequence) under the same definition, sequence q being
+ * phrase_words[phrase_off[q] .. phrase_off[q+1]); a sequence never seen or of
+ * a length outside [min_len, max_len] counts 0.  It builds the table the same
+ * way, in the same passes, and keeps nothing from an earlier call.
+ * lda_phrase_lookup is lda_phrase_counts that also returns, in first[q]
+ * (NULL: not wanted), the smallest shard-local start of the phrase, -1 where
+ * the count is 0: what a merge over shards needs.
+ * Errors, all checked on the host before any device work:
+ * LDA_ERR_INVALID_ARG for a NULL ctx or output, n outside
+ * [1, LDA_PHRASES_MAX], limits outside 2 <= min_len <= max_len <=
+ * LDA_PHRASE_LEN_MAX, min_count < 1, Q < 0, a query topic outside [0, K), a
+ * word id outside [0, V), phrase_off[0] != 0 or a decreasing phrase_off;
+ * LDA_ERR_STATE with a pending delta (call lda_apply first);
+ * LDA_ERR_UNSUPPORTED for a shard of 2^32 or more tokens (the counts are 32
+ * bits).  D = 0 or N = 0 succeeds with empty lists (all counts 0).
+ * LDA_ERR_INTERNAL if a pass filled its table, which the pass cut rules out
+ * unless one part alone holds more distinct phrases than half the slots.
+ * Device scratch is grow-only and kept by the context.  Waits once for the
+ * context's stream, and once more, for the per-part run counts, only when
+ * N / min_len exceeds half the largest table (or the test hook is set). */
+#define LDA_PHRASE_LEN_MAX 32
+#define LDA_PHRASES_MAX 128
+lda_status lda_topic_phrases(lda_ctx* ctx, int32_t n, int32_t min_len, int32_t max_len, int32_t min_count,
+                             int32_t* phrase_words /*[K*n*max_len], -1 padded*/, int32_t* lengths /*[K*n]*/,
+                             int64_t* counts /*[K*n]*/, int64_t* first /*[K*n]*/, int64_t* topic_runs /*[K]*/,
+                             int64_t* topic_distinct /*[K]*/, int64_t* skipped_long);
+lda_status lda_phrase_counts(lda_ctx* ctx, int32_t min_len, int32_t max_len, int64_t Q,
+                             const int32_t* topics /*[Q]*/, const int64_t* phrase_off /*[Q+1]*/,
+                             const int32_t* phrase_words, int64_t* counts /*[Q]*/);
+lda_status lda_phrase_lookup(lda_ctx* ctx, int32_t min_len, int32_t max_len, int64_t Q,
+                             const int32_t* topics /*[Q]*/, const int64_t* phrase_off /*[Q+1]*/,
+                             const int32_t* phrase_words, int64_t* counts /*[Q]*/, int64_t* first /*[Q] or NULL*/);
+/* Test hook: the phrase table has exactly `slots` slots (a power of two >= 2;
+ * 0 or anything else = the default), so that small inputs take many passes. */
+void lda_debug_phrase_table_slots(int64_t slots);
+
 /* Topic diagnostics: the integer statistics behind per-topic coherence,
  * document entropy, rank-1 documents, allocation ratio / count, exclusivity
  * and the distances from the uniform and corpus distributions, counted on the
@@ -880,8 +955,10 @@ void lda_debug_fail_host_alloc(int32_t nth);
  * lda_debug_ltr_chunk_cells), then lda_topic_distances, lda_topic_nearest
  * and lda_topic_distance_slabs, then lda_word_cooccurrences (with its test
  * hook lda_debug_cooc_chunk_tokens), then lda_topic_top_docs (with its test
- * hook lda_debug_topic_docs_chunk_docs) came later and only add symbols, so
- * the version stays 8. */
+ * hook lda_debug_topic_docs_chunk_docs), then lda_topic_phrases,
+ * lda_phrase_counts and lda_phrase_lookup (with their test hook
+ * lda_debug_phrase_table_slots) came later and only add symbols, so the
+ * version stays 8. */
 #define LDA_ABI_VERSION 8
 const char* lda_version(void);
 int32_t lda_abi_version(void);

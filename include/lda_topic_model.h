@@ -16,6 +16,7 @@
  *   printDocumentTopics(File)                     -> ldatm_print_document_topics
  *   printTopWords(File, n, newLines)              -> ldatm_print_top_words
  *   printTopicDocuments(File, max)                -> ldatm_print_topic_documents
+ *   topicPhraseXMLReport's phrases, as text       -> ldatm_print_topic_phrases
  *   getInferencer().getSampledDistribution(...)   -> ldatm_infer
  *   the predict loop's similarity to every
  *   training document (Predictor.predict)        -> ldatm_score / ldatm_score_theta / ldatm_score_top
@@ -406,6 +407,59 @@ lda_status ldatm_topic_documents_text(ldatm* m, int32_t max, double smoothing, i
 lda_status ldatm_topic_documents_format(int32_t K, int32_t n, double smoothing, const int64_t* doc_ids,
                                         const int32_t* counts, const int32_t* lengths, const char* const* names,
                                         int64_t num_names, char* buf, size_t cap, size_t* len);
+
+/* Topic phrases: each topic's most frequent same-topic token runs, counted on
+ * the device (lda_topic_phrases of lda_mi355x.h; the question
+ * Mallet's --xml-topic-phrase-report answers, by this library's definition: a
+ * run is a maximal range of consecutive tokens of one document with one
+ * topic, it qualifies with min_len <= length <= max_len, a longer run counts
+ * toward skipped_long alone; Mallet's own loop, as recalled and not tested
+ * against, never counts a run that reaches a document's last token and does
+ * not let a phrase's closing token start the next one).
+ * ldatm_topic_phrases: per topic k < K the first n phrases with count >=
+ * min_count by count descending, then word id sequence ascending, a prefix
+ * before its extension: phrase_words[K*n*max_len] (-1 padded), lengths[K*n],
+ * counts[K*n], first[K*n] (the smallest GLOBAL token index at which the phrase
+ * starts, tokens numbered through the documents in order), empty slots -1 / 0
+ * / 0 / -1; topic_runs[K] the qualifying runs, topic_distinct[K] the distinct
+ * phrases before min_count, *skipped_long the runs longer than max_len.
+ * One shard: lda_topic_phrases passed through, proven[k] = n.
+ * Several shards (contiguous document ranges): every shard lists its best
+ * LDA_PHRASES_MAX = 128 phrases per topic; the lists are united by content;
+ * every candidate's exact total and smallest start come from
+ * lda_phrase_lookup on every shard; the candidates are ordered by the rule
+ * above on their totals.  A phrase outside the union is outside every shard's
+ * list, so its total is at most B_k = sum over the shards g of tau_g, tau_g
+ * being shard g's 128th count for the topic (0 if its list is not full).
+ * proven[k] is the number of leading entries whose total is strictly above
+ * B_k: those, in that order, are the topic's true leading phrases.  B_k = 0
+ * (no shard's list is full): the union is everything and proven[k] = n.
+ * topic_runs and skipped_long are sums over the shards; topic_distinct is not
+ * a sum, a phrase may live in several shards: it is -1 with several shards.
+ * Errors, checked before any device work: LDA_ERR_INVALID_ARG for a NULL
+ * model or output, n outside [1, LDA_PHRASES_MAX], limits outside 2 <= min_len
+ * <= max_len <= LDA_PHRASE_LEN_MAX, min_count < 1.
+ * ldatm_topic_phrases_text / ldatm_print_topic_phrases: the lists as text,
+ * "#topic rank count phrase\n", then per topic and rank (from 0)
+ * "<topic> <rank> <count> <word> <word> ...\n", single spaces, the alphabet's
+ * words (the ids without an alphabet); empty slots print nothing.
+ * ldatm_topic_phrases_format: that text from the caller's arrays (host only);
+ * names[num_names] names the words (NULL or no entry: the id).
+ * ldatm_topic_phrases_bound: B_k and proven[k] from the shards' listed counts
+ * shard_counts[shards][K][LDA_PHRASES_MAX] and totals[K*n] (host only). */
+lda_status ldatm_topic_phrases(ldatm* m, int32_t n, int32_t min_len, int32_t max_len, int32_t min_count,
+                               int32_t* phrase_words /*[K*n*max_len]*/, int32_t* lengths /*[K*n]*/,
+                               int64_t* counts /*[K*n]*/, int64_t* first /*[K*n]*/, int64_t* topic_runs /*[K]*/,
+                               int64_t* topic_distinct /*[K]*/, int64_t* skipped_long, int32_t* proven /*[K]*/);
+lda_status ldatm_topic_phrases_text(ldatm* m, int32_t n, int32_t min_len, int32_t max_len, int32_t min_count,
+                                    char* buf, size_t cap, size_t* len);
+lda_status ldatm_print_topic_phrases(ldatm* m, const char* path, int32_t n, int32_t min_len, int32_t max_len,
+                                     int32_t min_count);
+lda_status ldatm_topic_phrases_format(int32_t K, int32_t n, int32_t max_len, const int32_t* phrase_words,
+                                      const int32_t* lengths, const int64_t* counts, const char* const* names,
+                                      int64_t num_names, char* buf, size_t cap, size_t* len);
+lda_status ldatm_topic_phrases_bound(int32_t K, int32_t n, int32_t shards, const int64_t* shard_counts,
+                                     const int64_t* totals, int64_t* bound /*[K]*/, int32_t* proven /*[K]*/);
 
 /* Checkpoint / resume: the reference's save()/load() of its model
  * (src/cmu_ron/TrainAndPredict.java:179-200) as a native binary file holding

@@ -36,6 +36,9 @@ TOP_WORDS_MAX = 64
 TOP_TOPICS_MAX = 64
 # LDA_TOPIC_DOCS_MAX of lda_mi355x.h
 TOPIC_DOCS_MAX = 128
+# LDA_PHRASE_LEN_MAX / LDA_PHRASES_MAX of lda_mi355x.h
+PHRASE_LEN_MAX = 32
+PHRASES_MAX = 128
 # LDA_DIAG_WORDS_MAX / LDA_DIAG_PROPS_MAX of lda_mi355x.h
 DIAG_WORDS_MAX = 64
 DIAG_PROPS_MAX = 8
@@ -183,6 +186,11 @@ SIGNATURES = {
     "lda_debug_cooc_chunk_tokens": (None, [C.c_int64]),
     "lda_topic_top_docs": (C.c_int32, [_vp, C.c_int32, C.c_double, C.c_int32, _vp, _vp, _vp]),
     "lda_debug_topic_docs_chunk_docs": (None, [C.c_int64]),
+    "lda_topic_phrases": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp]),
+    "lda_phrase_counts": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp, _vp]),
+    "lda_phrase_lookup": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "lda_debug_phrase_table_slots": (None, [C.c_int64]),
     "lda_topic_distances": (C.c_int32, [_vp, _vp, C.c_int32, _vp]),
     "lda_topic_nearest": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
     "lda_topic_distance_slabs": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),

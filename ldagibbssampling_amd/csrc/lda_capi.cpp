@@ -250,6 +250,17 @@ constexpr int64_t TOPIC_DOCS_WAVES = 1024;
 static_assert(LDA_TOPIC_DOCS_MAX == lda::TOPIC_DOCS_MAX, "the header states the kernels' limit");
 static_assert(TOPIC_DOCS_WAVES <= lda::TOPIC_DOCS_MAX_SLABS, "the merge holds every slab's head");
 int64_t g_topic_docs_chunk = 0;   // lda_debug_topic_docs_chunk_docs (0: TOPIC_DOCS_CELLS / Kp)
+// lda_topic_phrases / lda_phrase_counts: the table has the smallest power of
+// two of slots >= 2 * (N / min_len), between PHRASE_MIN_SLOTS and
+// PHRASE_MAX_SLOTS (12 bytes a slot: 3 GiB, and 4 more for the selection's
+// buckets); a pass fills at most half of it
+constexpr int64_t PHRASE_MIN_SLOTS = 1024;
+constexpr int64_t PHRASE_MAX_SLOTS = int64_t(1) << 28;
+static_assert(LDA_PHRASE_LEN_MAX == lda::PHRASE_LEN_MAX, "the header states the kernels' limit");
+static_assert(LDA_PHRASES_MAX == lda::PHRASES_MAX, "the header states the kernels' limit");
+static_assert(LDA_MAX_TOPICS <= (1 << lda::PHRASE_TOPIC_BITS), "a topic fits the key's topic field");
+static_assert(LDA_PHRASE_LEN_MAX <= (1 << lda::PHRASE_LEN_BITS), "length - 1 fits the key's length field");
+int64_t g_phrase_slots = 0;   // lda_debug_phrase_table_slots (0: sized from N)
 // lda_top_words' slab pass: at least TOP_WORDS_SLAB_ROWS rows per slab (a
 // slab's list warms up over its first rows), at most TOP_WORDS_WAVES (slab,
 // topic group) waves, which bounds the slab lists at TOP_WORDS_WAVES * 64 * n
@@ -394,6 +405,14 @@ struct lda_ctx {
   unsigned long long* td_bits = nullptr;
   int64_t *td_ids = nullptr, *td_out_ids = nullptr;
   size_t td_cap[6] = {};
+  // lda_topic_phrases / lda_phrase_counts: grow-only scratch -- the table
+  // (keys, counts), the selection's buckets, histogram and per-topic words,
+  // the carried lists, the result, and a call's queries
+  unsigned long long *ph_keys = nullptr, *ph_u64 = nullptr, *ph_sel_key = nullptr;
+  uint32_t *ph_cnts = nullptr, *ph_cand = nullptr, *ph_u32 = nullptr, *ph_hist = nullptr, *ph_sel_cnt = nullptr;
+  int32_t *ph_out32 = nullptr, *ph_q32 = nullptr;
+  int64_t *ph_out64 = nullptr, *ph_q64 = nullptr;
+  size_t ph_cap[12] = {};
   // 16-bit rows of the snapshot (LDA_SAMPLER_DENSE)
   uint16_t* nw16 = nullptr;
   uint8_t* wide = nullptr;
@@ -550,6 +569,8 @@ struct lda_ctx {
                     (void*)dg_ids, (void*)dg_table, (void*)dg_out, (void*)dg_shares,
                     (void*)cc_moff, (void*)cc_mem, (void*)cc_words, (void*)cc_out, (void*)cc_off,
                     (void*)td_rows, (void*)td_cnts, (void*)td_out, (void*)td_bits, (void*)td_ids, (void*)td_out_ids,
+                    (void*)ph_keys, (void*)ph_u64, (void*)ph_sel_key, (void*)ph_cnts, (void*)ph_cand, (void*)ph_u32,
+                    (void*)ph_hist, (void*)ph_sel_cnt, (void*)ph_out32, (void*)ph_q32, (void*)ph_out64, (void*)ph_q64,
                     (void*)perm, (void*)items, (void*)warm.range_doc, (void*)steady.range_doc,
                     (void*)big.tab, (void*)big.tab_m1, (void*)big.F, (void*)big.pfx, (void*)big.scal})
       if (p) (void)hipFree(p);
@@ -2564,6 +2585,8 @@ hipError_t grow_bytes(void** ptr, size_t* cap, size_t bytes) {
   grow_bytes(reinterpret_cast<void**>(&(ptr)), &(c)->cc_cap[(slot)], (n) * sizeof(*(ptr)))
 #define td_need(c, ptr, n, slot) \
   grow_bytes(reinterpret_cast<void**>(&(ptr)), &(c)->td_cap[(slot)], (n) * sizeof(*(ptr)))
+#define ph_need(c, ptr, n, slot) \
+  grow_bytes(reinterpret_cast<void**>(&(ptr)), &(c)->ph_cap[(slot)], (n) * sizeof(*(ptr)))
 
 // the document arguments lda_score_docs takes, checked the same way
 lda_status check_doc_list(const lda_ctx* c, int64_t doc_begin, int64_t M, const int64_t* docs) {
@@ -2759,6 +2782,230 @@ lda_status lda_topic_top_docs(lda_ctx* c, int32_t n, double smoothing, int32_t m
   HIP_TRY(hipStreamSynchronize(c->stream));
   return LDA_OK;
   });
+}
+
+void lda_debug_phrase_table_slots(int64_t slots) {
+  g_phrase_slots = slots >= 2 && (slots & (slots - 1)) == 0 && slots <= PHRASE_MAX_SLOTS ? slots : 0;
+}
+
+namespace {
+
+lda_status check_phrase_limits(int32_t min_len, int32_t max_len) {
+  if (min_len < 2 || min_len > max_len || max_len > LDA_PHRASE_LEN_MAX)
+    return fail(LDA_ERR_INVALID_ARG, "the lengths must satisfy 2 <= min_len <= max_len <= LDA_PHRASE_LEN_MAX");
+  return LDA_OK;
+}
+
+// The table and the run scan shared by lda_topic_phrases and
+// lda_phrase_lookup: sizes the table, allocates the scratch every pass needs,
+// counts the runs (per topic, too long, per hash part) and cuts the parts
+// into passes of at most slots / 2 qualifying runs each: cuts[p] .. cuts[p+1]
+// are pass p's parts.  One part alone above the half is a pass of its own
+// (its runs bound its distinct phrases from above; if those fill the table
+// the insert raises the flag).
+lda_status phrase_prepare(lda_ctx* c, lda::PhraseArgs& a, int32_t min_len, int32_t max_len,
+                          std::vector<int32_t>& cuts) {
+  const int64_t bound = c->N / min_len;   // no more qualifying runs than this
+  int64_t slots = g_phrase_slots;
+  if (!slots) {
+    slots = PHRASE_MIN_SLOTS;
+    while (slots < 2 * bound && slots < PHRASE_MAX_SLOTS) slots *= 2;
+  }
+  const size_t K = (size_t)c->K;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(ph_need(c, c->ph_keys, (size_t)slots, 0));
+  HIP_TRY(ph_need(c, c->ph_cnts, (size_t)slots, 1));
+  HIP_TRY(ph_need(c, c->ph_u64, 2 * K + 1, 2));
+  HIP_TRY(ph_need(c, c->ph_u32, (size_t)lda::PHRASE_PARTS + 1 + 4 * K, 3));
+  a = lda::PhraseArgs{};
+  a.words = c->words;
+  a.z = c->z;
+  a.doc_off = c->doc_off;
+  a.D = c->D;
+  a.K = c->K;
+  a.min_len = min_len;
+  a.max_len = max_len;
+  a.part_lo = 0;
+  a.part_hi = lda::PHRASE_PARTS;
+  a.slots = slots;
+  a.keys = c->ph_keys;
+  a.cnts = c->ph_cnts;
+  a.topic_runs = c->ph_u64;
+  a.topic_distinct = c->ph_u64 + K;
+  a.skipped_long = c->ph_u64 + 2 * K;
+  a.part_runs = c->ph_u32;
+  a.flag = c->ph_u32 + lda::PHRASE_PARTS;
+  a.thr = a.flag + 1;
+  a.bucket_off = a.thr + K;
+  a.cursor = a.bucket_off + K;
+  a.sel_len = reinterpret_cast<int32_t*>(a.cursor + K);
+  HIP_TRY(hipMemsetAsync(c->ph_u64, 0, sizeof(unsigned long long) * (2 * K + 1), c->stream));
+  HIP_TRY(hipMemsetAsync(c->ph_u32, 0, sizeof(uint32_t) * ((size_t)lda::PHRASE_PARTS + 1 + 4 * K), c->stream));
+  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((c->D + 3) / 4, (int64_t)c->cus * 8));
+  HIP_TRY(lda::launch_phrase_scan(a, blocks, c->stream));
+  cuts.assign({0, lda::PHRASE_PARTS});
+  if (bound > slots / 2) {
+    std::vector<uint32_t> runs((size_t)lda::PHRASE_PARTS);
+    HIP_TRY(hipMemcpyAsync(runs.data(), a.part_runs, sizeof(uint32_t) * runs.size(), hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    cuts.assign(1, 0);
+    int64_t in_pass = 0;
+    for (int32_t p = 0; p < lda::PHRASE_PARTS; ++p) {
+      if (in_pass > 0 && in_pass + runs[(size_t)p] > slots / 2) {
+        cuts.push_back(p);
+        in_pass = 0;
+      }
+      in_pass += runs[(size_t)p];
+    }
+    cuts.push_back(lda::PHRASE_PARTS);
+  }
+  return LDA_OK;
+}
+
+// pass p's table: cleared, then filled with the runs of its parts
+lda_status phrase_fill(lda_ctx* c, lda::PhraseArgs& a, const std::vector<int32_t>& cuts, size_t p) {
+  a.part_lo = cuts[p];
+  a.part_hi = cuts[p + 1];
+  a.first = p == 0;
+  HIP_TRY(hipMemsetAsync(a.keys, 0xff, sizeof(unsigned long long) * (size_t)a.slots, c->stream));
+  HIP_TRY(hipMemsetAsync(a.cnts, 0, sizeof(uint32_t) * (size_t)a.slots, c->stream));
+  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((c->D + 3) / 4, (int64_t)c->cus * 8));
+  HIP_TRY(lda::launch_phrase_insert(a, blocks, c->stream));
+  return LDA_OK;
+}
+
+}  // namespace
+
+lda_status lda_topic_phrases(lda_ctx* c, int32_t n, int32_t min_len, int32_t max_len, int32_t min_count,
+                             int32_t* phrase_words, int32_t* lengths, int64_t* counts, int64_t* first,
+                             int64_t* topic_runs, int64_t* topic_distinct, int64_t* skipped_long) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (n < 1 || n > LDA_PHRASES_MAX) return fail(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_PHRASES_MAX]");
+  if (lda_status st = check_phrase_limits(min_len, max_len)) return st;
+  if (min_count < 1) return fail(LDA_ERR_INVALID_ARG, "min_count must be at least 1");
+  if (!phrase_words || !lengths || !counts || !first || !topic_runs || !topic_distinct || !skipped_long)
+    return fail(LDA_ERR_INVALID_ARG, "null output");
+  if (c->pending) return fail(LDA_ERR_STATE, "topic phrases with a pending delta: call lda_apply first");
+  if (c->N >= (int64_t(1) << 32)) return fail(LDA_ERR_UNSUPPORTED, "topic phrases: 2^32 or more tokens in a shard");
+  const size_t K = (size_t)c->K, cells = K * (size_t)n;
+  if (c->D == 0 || c->N == 0) {
+    std::fill(phrase_words, phrase_words + cells * (size_t)max_len, -1);
+    std::fill(lengths, lengths + cells, 0);
+    std::fill(counts, counts + cells, (int64_t)0);
+    std::fill(first, first + cells, (int64_t)-1);
+    std::fill(topic_runs, topic_runs + K, (int64_t)0);
+    std::fill(topic_distinct, topic_distinct + K, (int64_t)0);
+    *skipped_long = 0;
+    return LDA_OK;
+  }
+  lda::PhraseArgs a;
+  std::vector<int32_t> cuts;
+  if (lda_status st = phrase_prepare(c, a, min_len, max_len, cuts)) return st;
+  HIP_TRY(ph_need(c, c->ph_cand, (size_t)a.slots, 4));
+  HIP_TRY(ph_need(c, c->ph_hist, K * lda::PHRASE_HIST_CAP, 5));
+  HIP_TRY(ph_need(c, c->ph_sel_key, cells, 6));
+  HIP_TRY(ph_need(c, c->ph_sel_cnt, cells, 7));
+  HIP_TRY(ph_need(c, c->ph_out32, cells * (size_t)max_len + cells, 8));
+  HIP_TRY(ph_need(c, c->ph_out64, 2 * cells, 9));
+  a.n = n;
+  a.min_count = min_count;
+  a.cand = c->ph_cand;
+  a.hist = c->ph_hist;
+  a.sel_key = c->ph_sel_key;
+  a.sel_cnt = c->ph_sel_cnt;
+  a.out_words = c->ph_out32;
+  a.out_lengths = c->ph_out32 + cells * (size_t)max_len;
+  a.out_counts = reinterpret_cast<long long*>(c->ph_out64);
+  a.out_first = reinterpret_cast<long long*>(c->ph_out64 + cells);
+  // the stream orders the passes: a pass's selection has read the table
+  // before the next pass clears it
+  for (size_t p = 0; p + 1 < cuts.size(); ++p) {
+    if (lda_status st = phrase_fill(c, a, cuts, p)) return st;
+    HIP_TRY(hipMemsetAsync(a.hist, 0, sizeof(uint32_t) * K * lda::PHRASE_HIST_CAP, c->stream));
+    HIP_TRY(lda::launch_phrase_select(a, c->cus * 8, c->stream));
+  }
+  HIP_TRY(lda::launch_phrase_gather(a, c->stream));
+  uint32_t flag = 0;
+  static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counters copy as int64");
+  HIP_TRY(hipMemcpyAsync(phrase_words, a.out_words, sizeof(int32_t) * cells * (size_t)max_len, hipMemcpyDeviceToHost,
+                         c->stream));
+  HIP_TRY(hipMemcpyAsync(lengths, a.out_lengths, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(counts, a.out_counts, sizeof(int64_t) * cells, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(first, a.out_first, sizeof(int64_t) * cells, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(topic_runs, a.topic_runs, sizeof(int64_t) * K, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(topic_distinct, a.topic_distinct, sizeof(int64_t) * K, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(skipped_long, a.skipped_long, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(&flag, a.flag, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (flag) return fail(LDA_ERR_INTERNAL, "topic phrases: a pass filled the phrase table");
+  return LDA_OK;
+  });
+}
+
+lda_status lda_phrase_lookup(lda_ctx* c, int32_t min_len, int32_t max_len, int64_t Q, const int32_t* topics,
+                             const int64_t* phrase_off, const int32_t* phrase_words, int64_t* counts,
+                             int64_t* first) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (lda_status st = check_phrase_limits(min_len, max_len)) return st;
+  if (Q < 0) return fail(LDA_ERR_INVALID_ARG, "Q must not be negative");
+  if (Q > 0 && (!topics || !phrase_off || !counts)) return fail(LDA_ERR_INVALID_ARG, "null query or output");
+  if (Q > 0 && phrase_off[0] != 0) return fail(LDA_ERR_INVALID_ARG, "phrase_off[0] must be 0");
+  for (int64_t q = 0; q < Q; ++q) {
+    if (topics[q] < 0 || topics[q] >= c->K) return fail(LDA_ERR_INVALID_ARG, "query topic out of range [0, K)");
+    if (phrase_off[q + 1] < phrase_off[q]) return fail(LDA_ERR_INVALID_ARG, "phrase_off must not decrease");
+  }
+  const int64_t W = Q > 0 ? phrase_off[Q] : 0;
+  if (W > 0 && !phrase_words) return fail(LDA_ERR_INVALID_ARG, "null phrase_words");
+  for (int64_t i = 0; i < W; ++i)
+    if (phrase_words[i] < 0 || phrase_words[i] >= c->V)
+      return fail(LDA_ERR_INVALID_ARG, "word id out of range [0, V)");
+  if (c->pending) return fail(LDA_ERR_STATE, "phrase counts with a pending delta: call lda_apply first");
+  if (c->N >= (int64_t(1) << 32)) return fail(LDA_ERR_UNSUPPORTED, "phrase counts: 2^32 or more tokens in a shard");
+  if (Q == 0) return LDA_OK;
+  std::fill(counts, counts + Q, (int64_t)0);
+  if (first) std::fill(first, first + Q, (int64_t)-1);
+  if (c->D == 0 || c->N == 0) return LDA_OK;
+  lda::PhraseArgs a;
+  std::vector<int32_t> cuts;
+  if (lda_status st = phrase_prepare(c, a, min_len, max_len, cuts)) return st;
+  HIP_TRY(ph_need(c, c->ph_q32, (size_t)(Q + std::max<int64_t>(W, 1)), 10));
+  HIP_TRY(ph_need(c, c->ph_q64, (size_t)(3 * Q + 1), 11));
+  int32_t* q_topics = c->ph_q32;
+  int32_t* q_words = c->ph_q32 + Q;
+  int64_t* q_off = c->ph_q64;
+  int64_t* q_counts = c->ph_q64 + Q + 1;
+  int64_t* q_first = q_counts + Q;
+  HIP_TRY(hipMemcpyAsync(q_topics, topics, sizeof(int32_t) * Q, hipMemcpyHostToDevice, c->stream));
+  if (W > 0) HIP_TRY(hipMemcpyAsync(q_words, phrase_words, sizeof(int32_t) * W, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(q_off, phrase_off, sizeof(int64_t) * (Q + 1), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(q_counts, 0, sizeof(int64_t) * Q, c->stream));
+  HIP_TRY(hipMemsetAsync(q_first, 0xff, sizeof(int64_t) * Q, c->stream));
+  a.Q = Q;
+  a.q_topics = q_topics;
+  a.q_off = q_off;
+  a.q_words = q_words;
+  a.q_counts = reinterpret_cast<long long*>(q_counts);
+  a.q_first = reinterpret_cast<long long*>(q_first);
+  for (size_t p = 0; p + 1 < cuts.size(); ++p) {
+    if (lda_status st = phrase_fill(c, a, cuts, p)) return st;
+    HIP_TRY(lda::launch_phrase_lookup(a, c->stream));
+  }
+  uint32_t flag = 0;
+  HIP_TRY(hipMemcpyAsync(counts, q_counts, sizeof(int64_t) * Q, hipMemcpyDeviceToHost, c->stream));
+  if (first) HIP_TRY(hipMemcpyAsync(first, q_first, sizeof(int64_t) * Q, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(&flag, a.flag, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (flag) return fail(LDA_ERR_INTERNAL, "phrase counts: a pass filled the phrase table");
+  return LDA_OK;
+  });
+}
+
+lda_status lda_phrase_counts(lda_ctx* c, int32_t min_len, int32_t max_len, int64_t Q, const int32_t* topics,
+                             const int64_t* phrase_off, const int32_t* phrase_words, int64_t* counts) {
+  return lda_phrase_lookup(c, min_len, max_len, Q, topics, phrase_off, phrase_words, counts, nullptr);
 }
 
 namespace {

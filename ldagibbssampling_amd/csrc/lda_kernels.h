@@ -512,4 +512,88 @@ hipError_t launch_count_hist(const int32_t* nw, int64_t V, int32_t K, int32_t Kp
 hipError_t launch_infer_init(const int32_t* words, int32_t* z, int64_t n, const int32_t* nw,
                              int32_t K, int32_t Kp, hipStream_t st);
 
+// lda_topic_phrases / lda_phrase_counts.  A run is a maximal
+// range of consecutive tokens of one document with one topic; it qualifies
+// with min_len <= length <= max_len.  Every pass over the runs recomputes
+// them from z and doc_off: a wave takes a document, a lane a token, the lane
+// of a run's first token walks at most max_len further tokens.  No pass keeps
+// a list of runs.
+//   launch_phrase_scan    counts per topic the qualifying runs, the runs
+//                         longer than max_len, and per hash part (the top
+//                         PHRASE_PART_BITS bits of a run's 64-bit hash) the
+//                         qualifying runs, from which the host cuts the passes
+//   launch_phrase_insert  inserts the qualifying runs whose part lies in
+//                         [part_lo, part_hi) into the table: open addressing,
+//                         linear probing, slots a power of two, a slot one
+//                         64-bit key (topic : 12 | length - 1 : 5 | start :
+//                         47; all ones = empty) and one 32-bit count.  An
+//                         empty slot is claimed by one 64-bit compare-and-swap;
+//                         an occupied one is compared by content through the
+//                         read-only words at its start, so nothing waits for
+//                         another lane.  A match adds 1 and takes the minimum
+//                         key, that is the smallest start.  A probe sequence
+//                         ends after `slots` steps and sets flag[0].
+//   launch_phrase_select  the pass's selection: a per-topic histogram of
+//                         min(count, PHRASE_HIST_CAP) and the topic's distinct
+//                         phrases; per topic the largest threshold >= min_count
+//                         with n phrases at or above it and the bucket offsets;
+//                         the scatter of the slots at or above the threshold;
+//                         then one wave per topic folds its bucket into the
+//                         topic's carried best-n list (sel_key / sel_cnt /
+//                         sel_len; first != 0: the lists start empty) by
+//                         count descending, then word sequence ascending, a
+//                         prefix before its extension.
+//   launch_phrase_gather  the lists as words / lengths / counts / starts
+//   launch_phrase_lookup  one probe sequence per query (topic, word sequence)
+//                         whose part lies in the pass
+constexpr int PHRASE_LEN_MAX = 32;
+constexpr int PHRASES_MAX = 128;
+constexpr int PHRASE_TOPIC_BITS = 12, PHRASE_LEN_BITS = 5, PHRASE_START_BITS = 47;
+constexpr int PHRASE_PART_BITS = 12;
+constexpr int PHRASE_PARTS = 1 << PHRASE_PART_BITS;
+constexpr int PHRASE_HIST_CAP = 256;
+constexpr unsigned long long PHRASE_EMPTY = ~0ull;
+static_assert(PHRASE_TOPIC_BITS + PHRASE_LEN_BITS + PHRASE_START_BITS == 64, "the key is one 64-bit word");
+static_assert((1 << PHRASE_LEN_BITS) >= PHRASE_LEN_MAX, "length - 1 fits its field");
+struct PhraseArgs {
+  const int32_t* words;
+  const int32_t* z;
+  const int64_t* doc_off;
+  int64_t D;
+  int32_t K, n, min_len, max_len, min_count;
+  int32_t part_lo, part_hi, first;
+  int64_t slots;                     // a power of two
+  unsigned long long* keys;          // [slots]
+  uint32_t* cnts;                    // [slots]
+  uint32_t* cand;                    // [slots]: the slots scattered into per-topic buckets
+  uint32_t* part_runs;               // [PHRASE_PARTS]
+  unsigned long long* topic_runs;    // [K]
+  unsigned long long* topic_distinct;// [K]
+  unsigned long long* skipped_long;  // [1]
+  uint32_t* flag;                    // [1]: a probe sequence found the table full
+  uint32_t* hist;                    // [K * PHRASE_HIST_CAP]
+  uint32_t* thr;                     // [K]
+  uint32_t* bucket_off;              // [K]
+  uint32_t* cursor;                  // [K]
+  unsigned long long* sel_key;       // [K * n]
+  uint32_t* sel_cnt;                 // [K * n]
+  int32_t* sel_len;                  // [K]
+  int32_t* out_words;                // [K * n * max_len]
+  int32_t* out_lengths;              // [K * n]
+  long long* out_counts;             // [K * n]
+  long long* out_first;              // [K * n]
+  // lookup
+  int64_t Q;
+  const int32_t* q_topics;           // [Q]
+  const int64_t* q_off;              // [Q + 1]
+  const int32_t* q_words;
+  long long* q_counts;               // [Q], zeroed by the caller
+  long long* q_first;                // [Q], -1 by the caller
+};
+hipError_t launch_phrase_scan(const PhraseArgs& a, int blocks, hipStream_t st);
+hipError_t launch_phrase_insert(const PhraseArgs& a, int blocks, hipStream_t st);
+hipError_t launch_phrase_select(const PhraseArgs& a, int blocks, hipStream_t st);
+hipError_t launch_phrase_gather(const PhraseArgs& a, hipStream_t st);
+hipError_t launch_phrase_lookup(const PhraseArgs& a, hipStream_t st);
+
 }  // namespace lda

@@ -5483,4 +5483,341 @@ hipError_t launch_topic_docs_merge(const TopicDocsArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// ---- lda_topic_phrases / lda_phrase_counts ----------------
+
+constexpr unsigned long long PHRASE_START_MASK = (1ull << PHRASE_START_BITS) - 1;
+
+__device__ __forceinline__ unsigned long long phrase_mix(unsigned long long h) {
+  h ^= h >> 33;
+  h *= 0xff51afd7ed558ccdull;
+  h ^= h >> 33;
+  h *= 0xc4ceb9fe1a85ec53ull;
+  h ^= h >> 33;
+  return h;
+}
+
+// the hash of (topic, w[0 .. len)): its top PHRASE_PART_BITS bits name the
+// part (the pass), its low bits the first slot
+__device__ __forceinline__ unsigned long long phrase_hash(int32_t topic, const int32_t* __restrict__ w, int len) {
+  unsigned long long h = phrase_mix(((unsigned long long)(uint32_t)topic << 8) + (unsigned long long)len);
+  for (int j = 0; j < len; ++j) h = phrase_mix(h + 0x9e3779b97f4a7c15ull + (unsigned long long)(uint32_t)w[j]);
+  return h;
+}
+
+__device__ __forceinline__ unsigned long long phrase_key(int32_t topic, int len, int64_t start) {
+  return ((unsigned long long)(uint32_t)topic << (PHRASE_LEN_BITS + PHRASE_START_BITS)) |
+         ((unsigned long long)(len - 1) << PHRASE_START_BITS) | (unsigned long long)start;
+}
+__device__ __forceinline__ int phrase_key_len(unsigned long long key) {
+  return (int)((key >> PHRASE_START_BITS) & ((1u << PHRASE_LEN_BITS) - 1)) + 1;
+}
+
+// every run of the shard once: a wave takes a document, a lane a token; the
+// lane of a run's first token (the document's first, or one whose left
+// neighbour has another topic) walks right to the run's end, at most max_len
+// steps, and calls f(topic, start, len) with len == max_len + 1 for every
+// longer run.  Nothing crosses a document's end.
+template <class F>
+__device__ __forceinline__ void phrase_for_runs(const PhraseArgs& a, F f) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int32_t* __restrict__ z = a.z;
+  for (int64_t d = (int64_t)blockIdx.x * 4 + wid; d < a.D; d += (int64_t)gridDim.x * 4) {
+    const int64_t b = a.doc_off[d], e = a.doc_off[d + 1];
+    for (int64_t i = b + lane; i < e; i += 64) {
+      const int32_t k = z[i];
+      if (i > b && z[i - 1] == k) continue;
+      int len = 1;
+      while (len <= a.max_len && i + len < e && z[i + len] == k) ++len;
+      f(k, i, len);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_phrase_scan(const PhraseArgs a) {
+  phrase_for_runs(a, [&](int32_t k, int64_t s, int len) {
+    if (len > a.max_len) {
+      atomicAdd(a.skipped_long, 1ull);
+    } else if (len >= a.min_len) {
+      atomicAdd(&a.topic_runs[k], 1ull);
+      atomicAdd(&a.part_runs[phrase_hash(k, a.words + s, len) >> (64 - PHRASE_PART_BITS)], 1u);
+    }
+  });
+}
+
+// same topic, same length and the same words as the run at `start`
+__device__ __forceinline__ bool phrase_same(const int32_t* __restrict__ words, unsigned long long cur,
+                                            unsigned long long key, const int32_t* __restrict__ w, int len) {
+  if ((cur >> PHRASE_START_BITS) != (key >> PHRASE_START_BITS)) return false;
+  const int32_t* __restrict__ o = words + (cur & PHRASE_START_MASK);
+  for (int j = 0; j < len; ++j)
+    if (o[j] != w[j]) return false;
+  return true;
+}
+
+__global__ __launch_bounds__(256) void k_phrase_insert(const PhraseArgs a) {
+  const unsigned long long mask = (unsigned long long)a.slots - 1;
+  phrase_for_runs(a, [&](int32_t k, int64_t s, int len) {
+    if (len < a.min_len || len > a.max_len) return;
+    const int32_t* __restrict__ w = a.words + s;
+    const unsigned long long h = phrase_hash(k, w, len);
+    const int part = (int)(h >> (64 - PHRASE_PART_BITS));
+    if (part < a.part_lo || part >= a.part_hi) return;
+    const unsigned long long key = phrase_key(k, len, s);
+    unsigned long long slot = h & mask;
+    // at most `slots` probes: a full table raises the flag, it never loops
+    for (int64_t p = 0; p < a.slots; ++p, slot = (slot + 1) & mask) {
+      unsigned long long cur = __hip_atomic_load(&a.keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (cur == PHRASE_EMPTY) {
+        cur = atomicCAS(&a.keys[slot], PHRASE_EMPTY, key);
+        if (cur == PHRASE_EMPTY) {
+          atomicAdd(&a.cnts[slot], 1u);
+          return;
+        }
+      }
+      // whatever start the key holds is a true occurrence of its phrase
+      if (phrase_same(a.words, cur, key, w, len)) {
+        atomicAdd(&a.cnts[slot], 1u);
+        if (key < cur) atomicMin(&a.keys[slot], key);
+        return;
+      }
+    }
+    atomicOr(a.flag, 1u);
+  });
+}
+
+__global__ __launch_bounds__(256) void k_phrase_hist(const PhraseArgs a) {
+  for (int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x; s < a.slots; s += (int64_t)gridDim.x * 256) {
+    const unsigned long long key = a.keys[s];
+    if (key == PHRASE_EMPTY) continue;
+    const int k = (int)(key >> (PHRASE_LEN_BITS + PHRASE_START_BITS));
+    const uint32_t c = min(a.cnts[s], (uint32_t)PHRASE_HIST_CAP);
+    atomicAdd(&a.hist[(size_t)k * PHRASE_HIST_CAP + c - 1], 1u);
+    atomicAdd(&a.topic_distinct[k], 1ull);
+  }
+}
+
+// per topic the largest threshold t in [min(min_count, cap), cap] with at
+// least n of the pass's phrases at min(count, cap) >= t (the smallest t if
+// there is none), the phrases at or above it as the bucket's size, then the
+// buckets' offsets: one block, K <= 4096 topics
+__global__ __launch_bounds__(256) void k_phrase_thresh(const PhraseArgs a) {
+  __shared__ uint32_t size[1 << PHRASE_TOPIC_BITS];
+  const uint32_t tmin = (uint32_t)min(a.min_count, PHRASE_HIST_CAP);
+  for (int k = threadIdx.x; k < a.K; k += 256) {
+    const uint32_t* __restrict__ h = a.hist + (size_t)k * PHRASE_HIST_CAP;
+    uint32_t acc = 0, t = PHRASE_HIST_CAP;
+    for (;; --t) {
+      acc += h[t - 1];
+      if (acc >= (uint32_t)a.n || t == tmin) break;
+    }
+    a.thr[k] = t;
+    size[k] = acc;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t off = 0;
+    for (int k = 0; k < a.K; ++k) {
+      const uint32_t s = size[k];
+      size[k] = off;
+      off += s;
+    }
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < a.K; k += 256) {
+    a.bucket_off[k] = size[k];
+    a.cursor[k] = 0;
+  }
+}
+
+// the slots at or above their topic's threshold go to the topic's bucket; the
+// order inside a bucket races and nothing depends on it
+__global__ __launch_bounds__(256) void k_phrase_scatter(const PhraseArgs a) {
+  for (int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x; s < a.slots; s += (int64_t)gridDim.x * 256) {
+    const unsigned long long key = a.keys[s];
+    if (key == PHRASE_EMPTY) continue;
+    const int k = (int)(key >> (PHRASE_LEN_BITS + PHRASE_START_BITS));
+    const uint32_t c = a.cnts[s];
+    if (c < (uint32_t)a.min_count || min(c, (uint32_t)PHRASE_HIST_CAP) < a.thr[k]) continue;
+    a.cand[a.bucket_off[k] + atomicAdd(&a.cursor[k], 1u)] = (uint32_t)s;
+  }
+}
+
+// the order of a topic's phrases: count descending, then the word sequence
+// ascending, a proper prefix before its extension
+__device__ __forceinline__ bool phrase_before(const int32_t* __restrict__ words, uint32_t ca, unsigned long long ka,
+                                              uint32_t cb, unsigned long long kb) {
+  if (ca != cb) return ca > cb;
+  const int la = phrase_key_len(ka), lb = phrase_key_len(kb);
+  const int32_t* __restrict__ wa = words + (ka & PHRASE_START_MASK);
+  const int32_t* __restrict__ wb = words + (kb & PHRASE_START_MASK);
+  for (int j = 0; j < min(la, lb); ++j)
+    if (wa[j] != wb[j]) return wa[j] < wb[j];
+  return la < lb;
+}
+
+// one wave per topic: the topic's carried list (sorted, at most n) takes the
+// bucket's candidates 64 at a time.  A lane keeps its candidate if the list is
+// short or the candidate stands before the list's last entry; the kept ones
+// enter one after another, the wave counting the entries that stand before
+// the candidate (its position, the order being strict and total) and moving
+// the tail down by one.
+__global__ __launch_bounds__(64) void k_phrase_select(const PhraseArgs a) {
+  __shared__ unsigned long long lk[PHRASES_MAX], ck[64];
+  __shared__ uint32_t lc[PHRASES_MAX], cc[64];
+  const int lane = threadIdx.x, k = blockIdx.x, n = a.n;
+  const int32_t* __restrict__ words = a.words;
+  int m = a.first ? 0 : a.sel_len[k];
+  for (int i = lane; i < m; i += 64) {
+    lk[i] = a.sel_key[(size_t)k * n + i];
+    lc[i] = a.sel_cnt[(size_t)k * n + i];
+  }
+  __syncthreads();
+  const uint32_t off = a.bucket_off[k], size = a.cursor[k];
+  for (uint32_t base = 0; base < size; base += 64) {
+    const bool has = base + lane < size;
+    unsigned long long key = PHRASE_EMPTY;
+    uint32_t cnt = 0;
+    if (has) {
+      const uint32_t s = a.cand[off + base + lane];
+      key = a.keys[s];
+      cnt = a.cnts[s];
+    }
+    ck[lane] = key;
+    cc[lane] = cnt;
+    const bool keep = has && (m < n || phrase_before(words, cnt, key, lc[m - 1], lk[m - 1]));
+    unsigned long long todo = __ballot(keep);
+    __syncthreads();
+    while (todo) {
+      const int src = __ffsll((long long)todo) - 1;
+      todo &= todo - 1;
+      const unsigned long long bk = ck[src];
+      const uint32_t bc = cc[src];
+      int pos = 0;
+      for (int t = 0; t < 2; ++t) {
+        const int i = lane + 64 * t;
+        pos += __popcll(__ballot(i < m && phrase_before(words, lc[i], lk[i], bc, bk)));
+      }
+      if (pos >= n) continue;
+      const int nm = min(m + 1, n);
+      unsigned long long tk[2] = {0, 0};
+      uint32_t tc[2] = {0, 0};
+      for (int t = 0; t < 2; ++t) {
+        const int i = lane + 64 * t;
+        if (i >= pos && i < nm - 1) {
+          tk[t] = lk[i];
+          tc[t] = lc[i];
+        }
+      }
+      __syncthreads();
+      for (int t = 0; t < 2; ++t) {
+        const int i = lane + 64 * t;
+        if (i >= pos && i < nm - 1) {
+          lk[i + 1] = tk[t];
+          lc[i + 1] = tc[t];
+        }
+      }
+      if (lane == 0) {
+        lk[pos] = bk;
+        lc[pos] = bc;
+      }
+      m = nm;
+      __syncthreads();
+    }
+    __syncthreads();
+  }
+  for (int i = lane; i < m; i += 64) {
+    a.sel_key[(size_t)k * n + i] = lk[i];
+    a.sel_cnt[(size_t)k * n + i] = lc[i];
+  }
+  if (lane == 0) a.sel_len[k] = m;
+}
+
+__global__ __launch_bounds__(256) void k_phrase_gather(const PhraseArgs a) {
+  const int64_t cells = (int64_t)a.K * a.n;
+  for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < cells; o += (int64_t)gridDim.x * 256) {
+    const int k = (int)(o / a.n), i = (int)(o % a.n);
+    const bool has = i < a.sel_len[k];
+    const unsigned long long key = has ? a.sel_key[o] : 0ull;
+    const int len = has ? phrase_key_len(key) : 0;
+    const int64_t start = (int64_t)(key & PHRASE_START_MASK);
+    a.out_lengths[o] = len;
+    a.out_counts[o] = has ? (long long)a.sel_cnt[o] : 0ll;
+    a.out_first[o] = has ? (long long)start : -1ll;
+    for (int j = 0; j < a.max_len; ++j) a.out_words[o * a.max_len + j] = j < len ? a.words[start + j] : -1;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_phrase_lookup(const PhraseArgs a) {
+  const unsigned long long mask = (unsigned long long)a.slots - 1;
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < a.Q; q += (int64_t)gridDim.x * 256) {
+    const int64_t len64 = a.q_off[q + 1] - a.q_off[q];
+    if (len64 < a.min_len || len64 > a.max_len) continue;
+    const int len = (int)len64;
+    const int32_t k = a.q_topics[q];
+    const int32_t* __restrict__ w = a.q_words + a.q_off[q];
+    const unsigned long long h = phrase_hash(k, w, len);
+    const int part = (int)(h >> (64 - PHRASE_PART_BITS));
+    if (part < a.part_lo || part >= a.part_hi) continue;
+    const unsigned long long key = phrase_key(k, len, 0);
+    unsigned long long slot = h & mask;
+    for (int64_t p = 0; p < a.slots; ++p, slot = (slot + 1) & mask) {
+      const unsigned long long cur = a.keys[slot];
+      if (cur == PHRASE_EMPTY) break;
+      if (phrase_same(a.words, cur, key, w, len)) {
+        a.q_counts[q] = (long long)a.cnts[slot];
+        if (a.q_first) a.q_first[q] = (long long)(cur & PHRASE_START_MASK);
+        break;
+      }
+    }
+  }
+}
+
+namespace {
+bool phrase_args_ok(const PhraseArgs& a) {
+  return a.min_len >= 2 && a.min_len <= a.max_len && a.max_len <= PHRASE_LEN_MAX && a.slots >= 2 &&
+         (a.slots & (a.slots - 1)) == 0 && a.slots <= (int64_t(1) << 32) && a.part_lo >= 0 &&
+         a.part_lo <= a.part_hi && a.part_hi <= PHRASE_PARTS && a.K >= 1 && a.K <= (1 << PHRASE_TOPIC_BITS);
+}
+}  // namespace
+
+hipError_t launch_phrase_scan(const PhraseArgs& a, int blocks, hipStream_t st) {
+  if (!phrase_args_ok(a) || blocks < 1 || a.D < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_phrase_scan, dim3(blocks), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_phrase_insert(const PhraseArgs& a, int blocks, hipStream_t st) {
+  if (!phrase_args_ok(a) || blocks < 1 || a.D < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_phrase_insert, dim3(blocks), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_phrase_select(const PhraseArgs& a, int blocks, hipStream_t st) {
+  if (!phrase_args_ok(a) || blocks < 1 || a.n < 1 || a.n > PHRASES_MAX || a.min_count < 1) return hipErrorInvalidValue;
+  const int b = (int)std::min<int64_t>(blocks, (a.slots + 255) / 256);
+  hipLaunchKernelGGL(k_phrase_hist, dim3(b), dim3(256), 0, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_phrase_thresh, dim3(1), dim3(256), 0, st, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_phrase_scatter, dim3(b), dim3(256), 0, st, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_phrase_select, dim3(a.K), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_phrase_gather(const PhraseArgs& a, hipStream_t st) {
+  if (!phrase_args_ok(a) || a.n < 1 || a.n > PHRASES_MAX) return hipErrorInvalidValue;
+  const int64_t cells = (int64_t)a.K * a.n;
+  hipLaunchKernelGGL(k_phrase_gather, dim3((unsigned)std::min<int64_t>((cells + 255) / 256, 2048)), dim3(256), 0, st,
+                     a);
+  return hipGetLastError();
+}
+
+hipError_t launch_phrase_lookup(const PhraseArgs& a, hipStream_t st) {
+  if (!phrase_args_ok(a) || a.Q < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_phrase_lookup, dim3((unsigned)std::min<int64_t>((a.Q + 255) / 256, 2048)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
 }  // namespace lda

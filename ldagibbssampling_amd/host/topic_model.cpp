@@ -32,6 +32,7 @@
 #include <cstring>
 #include <fstream>
 #include <limits>
+#include <map>
 #include <numeric>
 #include <sstream>
 
@@ -1129,6 +1130,138 @@ std::string ParallelTopicModel::topicDocuments(int32_t max, double smoothing, in
   topicTopDocs(max, smoothing, min_tokens, ids.data(), cnt.data(), len.data());
   return topicDocumentsFormat(K_, max, smoothing, ids.data(), cnt.data(), len.data(), [&](int64_t d) {
     return has_source_[(size_t)d] ? sources_[(size_t)d] : std::string("null-source");
+  });
+}
+
+namespace {
+// lda_topic_phrases' argument checks, before any shard is built
+void checkTopicPhrases(int32_t n, int32_t min_len, int32_t max_len, int32_t min_count) {
+  if (n < 1 || n > LDA_PHRASES_MAX) raise(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_PHRASES_MAX]");
+  if (min_len < 2 || min_len > max_len || max_len > LDA_PHRASE_LEN_MAX)
+    raise(LDA_ERR_INVALID_ARG, "the lengths must satisfy 2 <= min_len <= max_len <= LDA_PHRASE_LEN_MAX");
+  if (min_count < 1) raise(LDA_ERR_INVALID_ARG, "min_count must be at least 1");
+}
+}  // namespace
+
+void topicPhrasesBound(int32_t K, int32_t n, int32_t G, const int64_t* shard_counts, const int64_t* totals,
+                       int64_t* bound, int32_t* proven) {
+  for (int32_t k = 0; k < K; ++k) {
+    int64_t B = 0;
+    for (int32_t g = 0; g < G; ++g) B += shard_counts[((size_t)g * K + k) * LDA_PHRASES_MAX + LDA_PHRASES_MAX - 1];
+    int32_t lead = 0;
+    while (lead < n && totals[(size_t)k * n + lead] > B) ++lead;
+    bound[k] = B;
+    proven[k] = B == 0 ? n : lead;
+  }
+}
+
+void ParallelTopicModel::topicPhrases(int32_t n, int32_t min_len, int32_t max_len, int32_t min_count,
+                                      int32_t* phrase_words, int32_t* lengths, int64_t* counts, int64_t* first,
+                                      int64_t* topic_runs, int64_t* topic_distinct, int64_t* skipped_long,
+                                      int32_t* proven) {
+  checkTopicPhrases(n, min_len, max_len, min_count);
+  if (!phrase_words || !lengths || !counts || !first || !topic_runs || !topic_distinct || !skipped_long || !proven)
+    raise(LDA_ERR_INVALID_ARG, "null output");
+  ensureShards();
+  const size_t G = shards_->ctx.size(), K = (size_t)K_, L = (size_t)max_len;
+  if (G == 1) {
+    check(lda_topic_phrases(shards_->ctx[0], n, min_len, max_len, min_count, phrase_words, lengths, counts, first,
+                            topic_runs, topic_distinct, skipped_long),
+          "lda_topic_phrases");
+    std::fill(proven, proven + K, n);
+    return;
+  }
+  // every shard's best LDA_PHRASES_MAX per topic, united by content; the
+  // candidates' exact totals and smallest starts from lda_phrase_lookup on
+  // every shard; then the order of lda_topic_phrases on the totals
+  const size_t M = LDA_PHRASES_MAX, cells = K * M;
+  std::vector<int32_t> sw(cells * L), sl(cells);
+  std::vector<int64_t> sc(G * cells), sf(cells), runs(K), distinct(K);
+  std::fill(topic_runs, topic_runs + K, (int64_t)0);
+  std::fill(topic_distinct, topic_distinct + K, (int64_t)-1);
+  *skipped_long = 0;
+  std::vector<std::map<std::vector<int32_t>, size_t>> seen(K);
+  std::vector<int32_t> q_topics, q_words;
+  std::vector<int64_t> q_off{0};
+  for (size_t g = 0; g < G; ++g) {
+    int64_t skipped = 0;
+    check(lda_topic_phrases(shards_->ctx[g], (int32_t)M, min_len, max_len, 1, sw.data(), sl.data(),
+                            sc.data() + g * cells, sf.data(), runs.data(), distinct.data(), &skipped),
+          "lda_topic_phrases");
+    *skipped_long += skipped;
+    for (size_t k = 0; k < K; ++k) {
+      topic_runs[k] += runs[k];
+      for (size_t i = 0; i < M && sl[k * M + i] > 0; ++i) {
+        const int32_t* w = sw.data() + (k * M + i) * L;
+        std::vector<int32_t> ph(w, w + sl[k * M + i]);
+        if (seen[k].emplace(ph, q_topics.size()).second) {
+          q_topics.push_back((int32_t)k);
+          q_words.insert(q_words.end(), ph.begin(), ph.end());
+          q_off.push_back((int64_t)q_words.size());
+        }
+      }
+    }
+  }
+  const size_t Q = q_topics.size();
+  std::vector<int64_t> total(Q, 0), start(Q, INT64_MAX), qc(Q), qf(Q);
+  for (size_t g = 0; g < G && Q > 0; ++g) {
+    check(lda_phrase_lookup(shards_->ctx[g], min_len, max_len, (int64_t)Q, q_topics.data(), q_off.data(),
+                            q_words.data(), qc.data(), qf.data()),
+          "lda_phrase_lookup");
+    const int64_t t0 = doc_off_[(size_t)shards_->doc_begin[g]];
+    for (size_t q = 0; q < Q; ++q) {
+      total[q] += qc[q];
+      if (qf[q] >= 0) start[q] = std::min(start[q], qf[q] + t0);
+    }
+  }
+  std::vector<std::pair<const std::vector<int32_t>*, size_t>> cand;
+  for (size_t k = 0; k < K; ++k) {
+    cand.clear();
+    for (const auto& e : seen[k])
+      if (total[e.second] >= min_count) cand.push_back({&e.first, e.second});
+    // the map iterates in word order (a prefix first): a stable sort by total
+    // descending leaves equal totals in that order
+    std::stable_sort(cand.begin(), cand.end(),
+                     [&](const auto& a, const auto& b) { return total[a.second] > total[b.second]; });
+    for (size_t i = 0; i < (size_t)n; ++i) {
+      const size_t o = k * (size_t)n + i;
+      const bool has = i < cand.size();
+      const size_t len = has ? cand[i].first->size() : 0;
+      for (size_t j = 0; j < L; ++j) phrase_words[o * L + j] = j < len ? (*cand[i].first)[j] : -1;
+      lengths[o] = (int32_t)len;
+      counts[o] = has ? total[cand[i].second] : 0;
+      first[o] = has ? start[cand[i].second] : -1;
+    }
+  }
+  std::vector<int64_t> bound(K);
+  topicPhrasesBound(K_, n, (int32_t)G, sc.data(), counts, bound.data(), proven);
+}
+
+std::string topicPhrasesFormat(int32_t K, int32_t n, int32_t max_len, const int32_t* phrase_words,
+                               const int32_t* lengths, const int64_t* counts,
+                               const std::function<std::string(int32_t)>& name) {
+  std::string out = "#topic rank count phrase\n";
+  for (int32_t k = 0; k < K; ++k)
+    for (int32_t i = 0; i < n; ++i) {
+      const size_t at = (size_t)k * n + i;
+      if (lengths[at] <= 0) break;
+      out += std::to_string(k) + " " + std::to_string(i) + " " + std::to_string(counts[at]);
+      for (int32_t j = 0; j < lengths[at]; ++j) out += " " + name(phrase_words[at * (size_t)max_len + j]);
+      out += "\n";
+    }
+  return out;
+}
+
+std::string ParallelTopicModel::topicPhrasesText(int32_t n, int32_t min_len, int32_t max_len, int32_t min_count) {
+  checkTopicPhrases(n, min_len, max_len, min_count);
+  const size_t K = (size_t)K_, cells = K * (size_t)n;
+  std::vector<int32_t> words(cells * (size_t)max_len), len(cells), proven(K);
+  std::vector<int64_t> cnt(cells), first(cells), runs(K), distinct(K);
+  int64_t skipped = 0;
+  topicPhrases(n, min_len, max_len, min_count, words.data(), len.data(), cnt.data(), first.data(), runs.data(),
+               distinct.data(), &skipped, proven.data());
+  return topicPhrasesFormat(K_, n, max_len, words.data(), len.data(), cnt.data(), [&](int32_t w) {
+    return alphabet_.empty() ? std::to_string(w) : alphabet_[(size_t)w];
   });
 }
 
@@ -2314,6 +2447,58 @@ lda_status ldatm_topic_documents_format(int32_t K, int32_t n, double smoothing, 
     });
   });
   return st ? st : copy_text(s, buf, cap, len);
+}
+
+lda_status ldatm_topic_phrases(ldatm* m, int32_t n, int32_t min_len, int32_t max_len, int32_t min_count,
+                               int32_t* phrase_words, int32_t* lengths, int64_t* counts, int64_t* first,
+                               int64_t* topic_runs, int64_t* topic_distinct, int64_t* skipped_long, int32_t* proven) {
+  TM_CHECK(m);
+  return guard([&] {
+    m->model.topicPhrases(n, min_len, max_len, min_count, phrase_words, lengths, counts, first, topic_runs,
+                          topic_distinct, skipped_long, proven);
+  });
+}
+
+lda_status ldatm_topic_phrases_text(ldatm* m, int32_t n, int32_t min_len, int32_t max_len, int32_t min_count,
+                                    char* buf, size_t cap, size_t* len) {
+  TM_CHECK(m);
+  std::string s;
+  lda_status st = guard([&] { s = m->model.topicPhrasesText(n, min_len, max_len, min_count); });
+  return st ? st : copy_text(s, buf, cap, len);
+}
+
+lda_status ldatm_print_topic_phrases(ldatm* m, const char* path, int32_t n, int32_t min_len, int32_t max_len,
+                                     int32_t min_count) {
+  TM_CHECK(m);
+  std::string s;
+  lda_status st = guard([&] { s = m->model.topicPhrasesText(n, min_len, max_len, min_count); });
+  return st ? st : write_file(path, s);
+}
+
+lda_status ldatm_topic_phrases_format(int32_t K, int32_t n, int32_t max_len, const int32_t* phrase_words,
+                                      const int32_t* lengths, const int64_t* counts, const char* const* names,
+                                      int64_t num_names, char* buf, size_t cap, size_t* len) {
+  if (K < 1 || n < 1 || max_len < 1 || !phrase_words || !lengths || !counts || num_names < 0 ||
+      (num_names > 0 && !names)) {
+    g_tm_error = "bad argument";
+    return LDA_ERR_INVALID_ARG;
+  }
+  std::string s;
+  lda_status st = guard([&] {
+    s = lda_host::topicPhrasesFormat(K, n, max_len, phrase_words, lengths, counts, [&](int32_t w) {
+      return w >= 0 && w < num_names && names[w] ? std::string(names[w]) : std::to_string(w);
+    });
+  });
+  return st ? st : copy_text(s, buf, cap, len);
+}
+
+lda_status ldatm_topic_phrases_bound(int32_t K, int32_t n, int32_t shards, const int64_t* shard_counts,
+                                     const int64_t* totals, int64_t* bound, int32_t* proven) {
+  if (K < 1 || n < 1 || n > LDA_PHRASES_MAX || shards < 1 || !shard_counts || !totals || !bound || !proven) {
+    g_tm_error = "bad argument";
+    return LDA_ERR_INVALID_ARG;
+  }
+  return guard([&] { lda_host::topicPhrasesBound(K, n, shards, shard_counts, totals, bound, proven); });
 }
 
 lda_status ldatm_save(ldatm* m, const char* path) {

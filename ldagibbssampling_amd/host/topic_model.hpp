@@ -48,6 +48,19 @@ double topicDocWeight(int32_t K, double smoothing, int32_t count, int32_t length
 std::string topicDocumentsFormat(int32_t K, int32_t n, double smoothing, const int64_t* doc_ids, const int32_t* counts,
                                  const int32_t* lengths, const std::function<std::string(int64_t)>& name);
 
+// lda_topic_phrases over several shards: B_k, the sum over
+// the shards of the count of the shard's last (LDA_PHRASES_MAX-th) listed
+// phrase of topic k (0 where the list is not full), bounds the total of every
+// phrase outside the united lists; proven[k] is the number of leading entries
+// of totals[k*n ..] strictly above B_k, n where B_k = 0.
+// shard_counts [G][K][LDA_PHRASES_MAX].  And printTopicPhrases' text from
+// K x n lists (host only; ldatm_topic_phrases_format of lda_topic_model.h).
+void topicPhrasesBound(int32_t K, int32_t n, int32_t G, const int64_t* shard_counts, const int64_t* totals,
+                       int64_t* bound, int32_t* proven);
+std::string topicPhrasesFormat(int32_t K, int32_t n, int32_t max_len, const int32_t* phrase_words,
+                               const int32_t* lengths, const int64_t* counts,
+                               const std::function<std::string(int32_t)>& name);
+
 class ParallelTopicModel {
  public:
   ParallelTopicModel(int32_t num_topics, double alpha_sum, double beta);
@@ -137,6 +150,18 @@ class ParallelTopicModel {
   // arguments are checked before any shard is built.
   void topicTopDocs(int32_t n, double smoothing, int32_t min_tokens, int64_t* doc_ids, int32_t* counts,
                     int32_t* lengths);
+
+  // lda_topic_phrases.  One shard: passed through, proven[k]
+  // = n.  Several: every shard's best LDA_PHRASES_MAX per topic united by
+  // content, the exact totals and smallest global starts of the candidates
+  // from lda_phrase_lookup on every shard, ordered as lda_topic_phrases
+  // orders them; topic_runs and skipped_long are sums, topic_distinct is -1
+  // (a phrase may live in several shards), proven as topicPhrasesBound.
+  void topicPhrases(int32_t n, int32_t min_len, int32_t max_len, int32_t min_count, int32_t* phrase_words,
+                    int32_t* lengths, int64_t* counts, int64_t* first, int64_t* topic_runs, int64_t* topic_distinct,
+                    int64_t* skipped_long, int32_t* proven);
+  // topicPhrases as text: "#topic rank count phrase", then "topic rank count w1 w2 ..."
+  std::string topicPhrasesText(int32_t n, int32_t min_len, int32_t max_len, int32_t min_count);
 
   // ---- topic diagnostics --------------------------------
   // lda_topic_codocuments on every shard with the caller's lists, summed in

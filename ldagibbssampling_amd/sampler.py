@@ -450,6 +450,57 @@ class GibbsSampler:
                                               cnt.ctypes.data, lens.ctypes.data), "lda_topic_top_docs")
         return docs, cnt, lens
 
+    def topic_phrases(self, n: int, min_len: int = 2, max_len: int = 32, min_count: int = 1):
+        """lda_topic_phrases: per topic the n most frequent same-topic token
+        runs (phrases) of this shard with min_len <= length <= max_len and
+        count >= min_count, by count descending, then word ids ascending, a
+        prefix before its extension, counted on the device from words and z.
+        Returns (words[K, n, max_len] int32 (-1 padded), lengths[K, n] int32,
+        counts[K, n] int64, first[K, n] int64 (smallest token index of the
+        phrase; -1 in an empty slot), runs[K] int64, distinct[K] int64,
+        skipped_long int)."""
+        n, min_len, max_len = int(n), int(min_len), int(max_len)
+        if not 1 <= n <= capi.PHRASES_MAX:
+            raise ValueError(f"n must be in [1, {capi.PHRASES_MAX}]")
+        if not 2 <= min_len <= max_len <= capi.PHRASE_LEN_MAX:
+            raise ValueError(f"the lengths must satisfy 2 <= min_len <= max_len <= {capi.PHRASE_LEN_MAX}")
+        words = np.zeros((self.K, n, max_len), dtype=np.int32)
+        lens = np.zeros((self.K, n), dtype=np.int32)
+        cnt = np.zeros((self.K, n), dtype=np.int64)
+        first = np.zeros((self.K, n), dtype=np.int64)
+        runs = np.zeros(self.K, dtype=np.int64)
+        distinct = np.zeros(self.K, dtype=np.int64)
+        skipped = C.c_int64()
+        capi.check(self._L.lda_topic_phrases(self._h, n, min_len, max_len, int(min_count), words.ctypes.data,
+                                             lens.ctypes.data, cnt.ctypes.data, first.ctypes.data, runs.ctypes.data,
+                                             distinct.ctypes.data, C.addressof(skipped)), "lda_topic_phrases")
+        return words, lens, cnt, first, runs, distinct, int(skipped.value)
+
+    def phrase_counts(self, topics, phrases, min_len: int = 2, max_len: int = 32, with_first: bool = False):
+        """lda_phrase_counts: the exact number of qualifying runs of each
+        (topics[q], phrases[q]) in this shard, phrases[q] a sequence of word
+        ids; 0 for one never seen or of a length outside [min_len, max_len].
+        Returns counts[Q] int64; with_first (lda_phrase_lookup) also the
+        smallest token index of each phrase, -1 where the count is 0."""
+        topics = np.ascontiguousarray(topics, dtype=np.int32).reshape(-1)
+        Q = len(topics)
+        if len(phrases) != Q:
+            raise ValueError("one phrase per topic entry")
+        off = np.zeros(Q + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(p) for p in phrases])
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(p, dtype=np.int32).reshape(-1) for p in phrases])
+                                    if Q else np.zeros(0), dtype=np.int32)
+        cnt = np.zeros(Q, dtype=np.int64)
+        first = np.full(Q, -1, dtype=np.int64)
+        if with_first:
+            capi.check(self._L.lda_phrase_lookup(self._h, int(min_len), int(max_len), Q, topics.ctypes.data,
+                                                 off.ctypes.data, flat.ctypes.data, cnt.ctypes.data,
+                                                 first.ctypes.data), "lda_phrase_lookup")
+            return cnt, first
+        capi.check(self._L.lda_phrase_counts(self._h, int(min_len), int(max_len), Q, topics.ctypes.data,
+                                             off.ctypes.data, flat.ctypes.data, cnt.ctypes.data), "lda_phrase_counts")
+        return cnt
+
     def _word_lists(self, word_ids):
         """(ids[K, n] int32, n) of K word lists, -1 = an empty slot."""
         ids = np.ascontiguousarray(word_ids, dtype=np.int32)

@@ -96,6 +96,12 @@ TM_SIGNATURES = {
     "ldatm_topic_documents_text": (_i32, [_vp, _i32, C.c_double, _i32, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "ldatm_topic_documents_format": (_i32, [_i32, _i32, C.c_double, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_size_t,
                                             C.POINTER(C.c_size_t)]),
+    "ldatm_topic_phrases": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ldatm_topic_phrases_text": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ldatm_print_topic_phrases": (_i32, [_vp, C.c_char_p, _i32, _i32, _i32, _i32]),
+    "ldatm_topic_phrases_format": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_size_t,
+                                          C.POINTER(C.c_size_t)]),
+    "ldatm_topic_phrases_bound": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "ldatm_save": (_i32, [_vp, C.c_char_p]),
     "ldatm_load": (_i32, [C.POINTER(_vp), C.c_char_p]),
     "ldatm_infer": (_i32, [_vp, C.c_int64, _i64p, _vp, _i32, _i32, _i32, C.c_uint64, _f64p]),
@@ -177,6 +183,57 @@ def format_topic_documents(docs, counts, lengths, smoothing: float = 10.0, names
     buf = C.create_string_buffer(size.value + 1)
     _check(L.ldatm_topic_documents_format(*args, buf, size.value + 1, C.byref(size)), "ldatm_topic_documents_format")
     return buf.value.decode()
+
+
+def format_topic_phrases(words, lengths, counts, names=None) -> str:
+    """ldatm_topic_phrases_format (host only, no device): printTopicPhrases'
+    text from words[K, n, max_len], lengths[K, n] and counts[K, n] as
+    topicPhrases returns them; names[w] is word w's text (None, or no entry:
+    the id)."""
+    w = np.ascontiguousarray(words, np.int32)
+    lens = np.ascontiguousarray(lengths, np.int32)
+    cnt = np.ascontiguousarray(counts, np.int64)
+    if w.ndim != 3 or lens.shape != w.shape[:2] or cnt.shape != w.shape[:2]:
+        raise ValueError("words must be [K, n, max_len], lengths and counts [K, n]")
+    K, n, max_len = w.shape
+    names = list(names or [])
+    arr = (C.c_char_p * max(len(names), 1))(*[None if s is None else str(s).encode() for s in names])
+    L = load_tm()
+    size = C.c_size_t()
+    args = (K, n, max_len, w.ctypes.data, lens.ctypes.data, cnt.ctypes.data, C.cast(arr, C.c_void_p), len(names))
+    _check(L.ldatm_topic_phrases_format(*args, None, 0, C.byref(size)), "ldatm_topic_phrases_format")
+    buf = C.create_string_buffer(size.value + 1)
+    _check(L.ldatm_topic_phrases_format(*args, buf, size.value + 1, C.byref(size)), "ldatm_topic_phrases_format")
+    return buf.value.decode()
+
+
+def topic_phrases_bound(shard_counts, totals):
+    """ldatm_topic_phrases_bound (host only): from the shards' listed counts
+    shard_counts[G, K, PHRASES_MAX] and the merged totals[K, n], (B[K] int64,
+    proven[K] int32): B_k sums the shards' 128th counts (0 for a list that is
+    not full) and bounds every phrase outside the united lists; proven[k] is
+    the number of leading totals strictly above B_k, n where B_k = 0."""
+    sc = np.ascontiguousarray(shard_counts, np.int64)
+    tot = np.ascontiguousarray(totals, np.int64)
+    if sc.ndim != 3 or sc.shape[2] != capi.PHRASES_MAX or tot.ndim != 2 or tot.shape[0] != sc.shape[1]:
+        raise ValueError("shard_counts must be [G, K, PHRASES_MAX] and totals [K, n]")
+    G, K, _ = sc.shape
+    bound = np.zeros(K, np.int64)
+    proven = np.zeros(K, np.int32)
+    _check(load_tm().ldatm_topic_phrases_bound(K, tot.shape[1], G, sc.ctypes.data, tot.ctypes.data,
+                                               bound.ctypes.data, proven.ctypes.data), "ldatm_topic_phrases_bound")
+    return bound, proven
+
+
+class TopicPhrases:
+    """getTopicPhrases' result: phrases[k] = [(text, count), ...], wordIds[k] =
+    [tuple of word ids, ...], counts[K, n], first[K, n] (smallest global token
+    index; -1 in an empty slot), runs[K], distinct[K] (-1 with several
+    shards), skippedLong, proven[K]."""
+
+    def __init__(self, phrases, wordIds, counts, first, runs, distinct, skippedLong, proven):
+        self.phrases, self.wordIds, self.counts, self.first = phrases, wordIds, counts, first
+        self.runs, self.distinct, self.skippedLong, self.proven = runs, distinct, skippedLong, proven
 
 
 class Alphabet:
@@ -515,6 +572,44 @@ class ParallelTopicModel:
         docs, w, _, _ = self.topicDocuments(n, smoothing, minTokens)
         return [[(int(d), float(x)) for d, x in zip(docs[k], w[k]) if d >= 0] for k in range(self.numTopics)]
 
+    # ------------------------------- topic phrases
+    def topicPhrases(self, n: int, minLength: int = 2, maxLength: int = 32, minCount: int = 1):
+        """ldatm_topic_phrases: per topic the n most frequent same-topic token
+        runs with minLength <= length <= maxLength and count >= minCount, by
+        count descending, then word ids ascending, a prefix before its
+        extension, counted on the device.  Returns (words[K, n, maxLength]
+        int32 (-1 padded), lengths[K, n] int32, counts[K, n] int64, first[K, n]
+        int64 global token index, runs[K] int64, distinct[K] int64 (-1 with
+        several shards), skippedLong int, proven[K] int32)."""
+        n, minLength, maxLength = int(n), int(minLength), int(maxLength)
+        if not 1 <= n <= capi.PHRASES_MAX:
+            raise ValueError(f"n must be in [1, {capi.PHRASES_MAX}]")
+        if not 2 <= minLength <= maxLength <= capi.PHRASE_LEN_MAX:
+            raise ValueError(f"the lengths must satisfy 2 <= minLength <= maxLength <= {capi.PHRASE_LEN_MAX}")
+        K = self.numTopics
+        words = np.zeros((K, n, maxLength), np.int32)
+        lens = np.zeros((K, n), np.int32)
+        cnt = np.zeros((K, n), np.int64)
+        first = np.zeros((K, n), np.int64)
+        runs = np.zeros(K, np.int64)
+        distinct = np.zeros(K, np.int64)
+        proven = np.zeros(K, np.int32)
+        skipped = C.c_int64()
+        _check(self._L.ldatm_topic_phrases(self._h, n, minLength, maxLength, int(minCount), words.ctypes.data,
+                                           lens.ctypes.data, cnt.ctypes.data, first.ctypes.data, runs.ctypes.data,
+                                           distinct.ctypes.data, C.addressof(skipped), proven.ctypes.data),
+               "topicPhrases")
+        return words, lens, cnt, first, runs, distinct, int(skipped.value), proven
+
+    def getTopicPhrases(self, n: int = 10, minLength: int = 2, maxLength: int = 32, minCount: int = 1) -> TopicPhrases:
+        words, lens, cnt, first, runs, distinct, skipped, proven = self.topicPhrases(n, minLength, maxLength, minCount)
+        name = str if self.alphabet is None else (lambda w: str(self.alphabet.lookupObject(w)))
+        ids = [[tuple(int(w) for w in words[k, i, :lens[k, i]]) for i in range(words.shape[1]) if lens[k, i] > 0]
+               for k in range(self.numTopics)]
+        phrases = [[(" ".join(name(w) for w in p), int(cnt[k, i])) for i, p in enumerate(ids[k])]
+                   for k in range(self.numTopics)]
+        return TopicPhrases(phrases, ids, cnt, first, runs, distinct, skipped, proven)
+
     # ------------------------------- topic distances (DESIGN 9g)
     def _other_model(self, other):
         """(native handle or None, K2) of the other side of a topic
@@ -728,6 +823,15 @@ class ParallelTopicModel:
     def printTopicDocuments(self, path, max: int = 100, smoothing: float = 10.0, minTokens: int = 1):
         _check(self._L.ldatm_print_topic_documents(self._h, os.fsencode(path), int(max), float(smoothing),
                                                    int(minTokens)), "printTopicDocuments")
+
+    def topicPhrasesText(self, n: int = 10, minLength: int = 2, maxLength: int = 32, minCount: int = 1) -> str:
+        """printTopicPhrases' text: "#topic rank count phrase", then per topic
+        and rank "topic rank count word word ..."."""
+        return self._text(self._L.ldatm_topic_phrases_text, int(n), int(minLength), int(maxLength), int(minCount))
+
+    def printTopicPhrases(self, path, n: int = 10, minLength: int = 2, maxLength: int = 32, minCount: int = 1):
+        _check(self._L.ldatm_print_topic_phrases(self._h, os.fsencode(path), int(n), int(minLength), int(maxLength),
+                                                 int(minCount)), "printTopicPhrases")
 
     # ------------------------------------------------ checkpoint / resume
     def save(self, path):
