@@ -597,6 +597,103 @@ lda_status lda_topic_top_docs(lda_ctx* ctx, int32_t n, double smoothing, int32_t
  * documents instead of 2^23 / Kp (0 = the default). */
 void lda_debug_topic_docs_chunk_docs(int64_t docs);
 
+/* Relevance-ranked topic words, salient terms and word rows: what an LDAvis
+ * view of a trained model shows, selected on the device from the global counts
+ * this shard holds (the int32 nw rows, V x Kp, and nwsum), without the V x K
+ * table leaving the device.  All fp64, one rounding per
+ * operation (the library is built without fast-math and with
+ * -ffp-contract=off):
+ *     tw[w]        = sum over k < K of nw[w,k]                    (int64)
+ *     N            = sum over k < K of nwsum[k]                   (int64)
+ *     logprob(w,k) = log(((double) nw[w,k] + beta) / ((double) nwsum[k] + Vbeta)),
+ *                    Vbeta = (double) V * beta
+ *     logtp(w)     = log((double) tw[w] / (double) N)
+ *     loglift(w,k) = logprob(w,k) - logtp(w)
+ *     key(w,k,l)   = logprob(w,k) - m * logtp(w),  m = 1.0 - lambda_l
+ * key is Sievert & Shirley's relevance lambda logprob + (1 - lambda) loglift
+ * written with one product; at lambda = 1 it is logprob exactly.  log is the
+ * device's fp64 log, which is not bit for bit the host libm's.
+ *
+ * lda_relevant_words: for each of L lambdas and each topic k < K (padded
+ * topics are never reported) the candidates are the words with nw[w,k] > 0
+ * (lda_top_words' candidates; tw > 0 follows), ordered by key descending,
+ * equal keys by ascending word id.  The first n of them go to plane l, row k:
+ * word_ids / counts (nw[w,k]) / totals (tw[w]) / logprob / loglift
+ * [(l * K + k) * n + i], i = 0 .. n-1; slots past the last candidate hold
+ * -1 / 0 / 0 / 0.0 / 0.0.  The same lambda may be passed more than once.
+ * The key's bits are mapped to a uint64 of the same order (every bit of a
+ * negative value flipped, else the sign bit set), and (key, word id) is unique
+ * per topic, so a topic's best n are one set however V is cut into slabs.  A
+ * lambda's plane is a function of that lambda, the table and (beta, V) alone:
+ * not of L, of the lambda's position, of how many lambdas a pass handles (8 up
+ * to n = 10, 4 up to n = 21, 2 up to n = 42, else 1: what 64 KiB of LDS hold
+ * at 12 bytes x 64 topics x n per list) or of the slabs; a call repeats bit
+ * for bit.  fp64 and integer compares only, no atomics.
+ * Errors, checked on the host in this order before any device work:
+ * LDA_ERR_INVALID_ARG for a NULL ctx, n outside [1, LDA_TOP_WORDS_MAX], L
+ * outside [1, LDA_RELEVANCE_LAMBDAS_MAX], a NULL lambdas, a lambda that is not
+ * finite or outside [0, 1], a NULL output; LDA_ERR_STATE with a pending delta
+ * (call lda_apply first).  V = 0 succeeds with -1 / 0 / 0 / 0.0 / 0.0
+ * everywhere.
+ * Cost: ceil(L / lambdas per pass) passes over nw; a cell with nw > 0 costs
+ * one division and one log per pass, a lambda a product, a difference and a
+ * compare more.
+ * Device scratch is grow-only and kept by the context.  tw and logtp take
+ * 16 V bytes (1/(4 Kp) of the nw table); everything else has a bound that
+ * depends on neither V nor N: the slab lists, at most 1024 (slab, 64-topic
+ * group) waves x 64 KiB (64 MiB), and a pass's planes, 32 bytes x K x n x
+ * lambdas per pass (at most 11 MiB), copied to the host pass by pass.  Waits
+ * once for the context's stream.
+ *
+ * lda_salient_words: the n most salient words (Chuang et al. 2012).  For a
+ * word with tw > 0
+ *     distinctiveness(w) = sum over k < K with nw[w,k] > 0 of q log(q / p_k),
+ *         q = (double) nw[w,k] / (double) tw[w],  p_k = (double) nwsum[k] / (double) N
+ *     saliency(w)        = ((double) tw[w] / (double) N) * distinctiveness(w)
+ * The sum is added in a fixed order that depends on the row alone: one wave
+ * per word, lane l adds the terms of k = l, l + 64, ... in ascending order
+ * from 0.0, then the 64 lane sums combine in the xor butterfly 32, 16, 8, 4,
+ * 2, 1 (lda_topic_word_stats' order).  The candidates, the words with tw > 0,
+ * are ordered by the saliency as computed, descending (a value a few ulp
+ * below 0 orders as the number it is; -0.0 as 0.0), equal values by ascending
+ * word id; the first n go to word_ids / totals (tw) / saliency /
+ * distinctiveness [i], slots past the last candidate hold -1 / 0 / 0.0 / 0.0.
+ * A call repeats bit for bit; no atomics.
+ * Errors, in this order before any device work: LDA_ERR_INVALID_ARG for a
+ * NULL ctx, n outside [1, LDA_SALIENT_WORDS_MAX], a NULL output;
+ * LDA_ERR_STATE with a pending delta.  V = 0 succeeds with the empty slots.
+ * Device scratch (shared with lda_relevant_words): tw, logtp and the
+ * distinctiveness, 24 V bytes; the slabs' lists, at most 1024 slabs x n
+ * entries of 12 bytes (3 MiB at n = 256), and the 24 n bytes of the result,
+ * whatever V and N are.  Waits once for the context's stream.
+ *
+ * lda_word_rows: the unpadded nw rows and totals of M listed words,
+ * rows[j*K + k] = nw[word_ids[j], k] (k < K) and totals[j] = tw[word_ids[j]];
+ * the list in any order, duplicates allowed.
+ * Errors, in this order before any device work: LDA_ERR_INVALID_ARG for a
+ * NULL ctx, M < 0, a NULL list with M > 0, an id outside [0, V), a NULL output
+ * with M > 0; LDA_ERR_STATE with a pending delta.  M = 0 then succeeds and
+ * touches nothing.
+ * The list goes through in chunks of at most max(1, 2^23 / K) rows, so the
+ * scratch never exceeds 32 MiB of rows + 12 bytes per row of the chunk (ids
+ * and totals), whatever M is.  Waits once for the context's stream. */
+#define LDA_RELEVANCE_LAMBDAS_MAX 128
+#define LDA_SALIENT_WORDS_MAX 256
+lda_status lda_relevant_words(lda_ctx* ctx, int32_t n, int32_t L, const double* lambdas /*[L]*/,
+                              int32_t* word_ids /*[L*K*n]*/, int32_t* counts /*[L*K*n]*/,
+                              int64_t* totals /*[L*K*n]*/, double* logprob /*[L*K*n]*/,
+                              double* loglift /*[L*K*n]*/);
+lda_status lda_salient_words(lda_ctx* ctx, int32_t n, int32_t* word_ids /*[n]*/, int64_t* totals /*[n]*/,
+                             double* saliency /*[n]*/, double* distinctiveness /*[n]*/);
+lda_status lda_word_rows(lda_ctx* ctx, int64_t M, const int32_t* word_ids /*[M]*/, int32_t* rows /*[M*K]*/,
+                         int64_t* totals /*[M]*/);
+/* Test hook: lda_relevant_words cuts V into slabs of `rows` rows (more rows
+ * where that would make more than 1024 slabs) instead of lda_top_words' cut,
+ * and lda_salient_words takes its slabs through LDS in chunks of
+ * min(rows, 1024) rows, four chunks to a slab, instead of one chunk of 1024
+ * (0 = the defaults). */
+void lda_debug_relevance_slab_rows(int64_t rows);
+
 /* lda_topic_phrases: the most frequent same-topic token runs of every topic of
  * THIS shard -- the question Mallet's --xml-topic-phrase-report
  * (topicPhraseXMLReport) answers -- counted on the device from the shard's
@@ -957,8 +1054,9 @@ void lda_debug_fail_host_alloc(int32_t nth);
  * hook lda_debug_cooc_chunk_tokens), then lda_topic_top_docs (with its test
  * hook lda_debug_topic_docs_chunk_docs), then lda_topic_phrases,
  * lda_phrase_counts and lda_phrase_lookup (with their test hook
- * lda_debug_phrase_table_slots) came later and only add symbols, so the
- * version stays 8. */
+ * lda_debug_phrase_table_slots), then lda_relevant_words, lda_salient_words
+ * and lda_word_rows (with their test hook lda_debug_relevance_slab_rows) came
+ * later and only add symbols, so the version stays 8. */
 #define LDA_ABI_VERSION 8
 const char* lda_version(void);
 int32_t lda_abi_version(void);

@@ -408,6 +408,51 @@ lda_status ldatm_topic_documents_format(int32_t K, int32_t n, double smoothing, 
                                         const int32_t* counts, const int32_t* lengths, const char* const* names,
                                         int64_t num_names, char* buf, size_t cap, size_t* len);
 
+/* Relevance-ranked topic words, salient terms and word rows: what an LDAvis
+ * view shows (lda_relevant_words, lda_salient_words and lda_word_rows of
+ * lda_mi355x.h, which states the definitions).  They run on shard 0
+ * as ldatm_top_words does: after the exchange every shard's nw is global, so
+ * the result does not depend on the number of shards.
+ * ldatm_relevant_words: planes [L][K][n] of word_ids / counts (nw[w,k]) /
+ * totals (tw[w]) / logprob / loglift, per lambda and topic the words with
+ * nw[w,k] > 0 by key = logprob - (1 - lambda) logtp descending, equal keys by
+ * ascending id; -1 / 0 / 0 / 0.0 / 0.0 past a topic's last candidate.
+ * ldatm_salient_words: the n words of largest saliency, descending, equal
+ * values by ascending id; -1 / 0 / 0.0 / 0.0 past the last word with a token.
+ * ldatm_word_rows: rows[M*K] and totals[M] of the listed words (any order,
+ * duplicates allowed); M = 0 succeeds and touches nothing.
+ * Errors, checked before any device work in the order of the sampler's calls
+ * (a model without documents or without a GPU names its bad argument):
+ * LDA_ERR_INVALID_ARG for a NULL model, n outside [1, LDA_TOP_WORDS_MAX]
+ * (salient: [1, LDA_SALIENT_WORDS_MAX]), L outside
+ * [1, LDA_RELEVANCE_LAMBDAS_MAX], a NULL lambdas, a lambda not finite or
+ * outside [0, 1], M < 0, a NULL list, a word id outside [0, V), a NULL output.
+ * Waits for shard 0's stream.
+ * ldatm_print_relevant_words / ldatm_relevant_words_text: the selection for
+ * one lambda as text, "#topic rank word count total relevance logprob
+ * loglift\n", then per topic and rank "<topic> <rank> <word> <nw[w,k]> <tw[w]>
+ * <relevance> <logprob> <loglift>\n" (the alphabet's word, else the id; the
+ * numbers as ldatm_format_double's Java Double.toString; relevance recomputed
+ * as logprob - (1 - lambda) (logprob - loglift)); padded slots print nothing.
+ * Same errors; buf / cap / len as the other *_text calls.
+ * ldatm_relevant_words_format: that text from the caller's K x n arrays (host
+ * only, no model and no device); names[num_names] gives the word column (NULL
+ * entry or an id >= num_names: the id). */
+lda_status ldatm_relevant_words(ldatm* m, int32_t n, int32_t L, const double* lambdas /*[L]*/,
+                                int32_t* word_ids /*[L*K*n]*/, int32_t* counts /*[L*K*n]*/,
+                                int64_t* totals /*[L*K*n]*/, double* logprob /*[L*K*n]*/,
+                                double* loglift /*[L*K*n]*/);
+lda_status ldatm_salient_words(ldatm* m, int32_t n, int32_t* word_ids /*[n]*/, int64_t* totals /*[n]*/,
+                               double* saliency /*[n]*/, double* distinctiveness /*[n]*/);
+lda_status ldatm_word_rows(ldatm* m, int64_t M, const int32_t* word_ids /*[M]*/, int32_t* rows /*[M*K]*/,
+                           int64_t* totals /*[M]*/);
+lda_status ldatm_print_relevant_words(ldatm* m, const char* path, int32_t n, double lambda);
+lda_status ldatm_relevant_words_text(ldatm* m, int32_t n, double lambda, char* buf, size_t cap, size_t* len);
+lda_status ldatm_relevant_words_format(int32_t K, int32_t n, double lambda, const int32_t* word_ids,
+                                       const int32_t* counts, const int64_t* totals, const double* logprob,
+                                       const double* loglift, const char* const* names, int64_t num_names,
+                                       char* buf, size_t cap, size_t* len);
+
 /* Topic phrases: each topic's most frequent same-topic token runs, counted on
  * the device (lda_topic_phrases of lda_mi355x.h; the question
  * Mallet's --xml-topic-phrase-report answers, by this library's definition: a

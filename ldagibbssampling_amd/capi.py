@@ -36,6 +36,9 @@ TOP_WORDS_MAX = 64
 TOP_TOPICS_MAX = 64
 # LDA_TOPIC_DOCS_MAX of lda_mi355x.h
 TOPIC_DOCS_MAX = 128
+# LDA_RELEVANCE_LAMBDAS_MAX / LDA_SALIENT_WORDS_MAX of lda_mi355x.h
+RELEVANCE_LAMBDAS_MAX = 128
+SALIENT_WORDS_MAX = 256
 # LDA_PHRASE_LEN_MAX / LDA_PHRASES_MAX of lda_mi355x.h
 PHRASE_LEN_MAX = 32
 PHRASES_MAX = 128
@@ -50,6 +53,29 @@ LTR_MAX_DOC_TOKENS = 4096
 # LDA_TOPIC_* metrics and LDA_TOPIC_NEAREST_MAX of lda_mi355x.h
 TOPIC_METRICS = {"cosine": 0, "hellinger": 1, "jensen_shannon": 2, "kullback_leibler": 3}
 TOPIC_NEAREST_MAX = 64
+
+
+def relevance_batch(n: int) -> int:
+    """The lambdas one pass of lda_relevant_words handles at list length n
+    (lda_mi355x.h): the largest of 8, 4, 2, 1 whose lists, 12 bytes x 64
+    topics x n each, fit 64 KiB of LDS.  Passes start at multiples of it."""
+    b = 8
+    while b > 1 and b * n * 64 * 12 > 64 * 1024:
+        b >>= 1
+    return b
+
+
+def check_lambdas(lambdas):
+    """lda_relevant_words' lambdas as a contiguous float64 array [L], refused
+    before any native call: 1 <= L <= RELEVANCE_LAMBDAS_MAX, each finite and
+    in [0, 1].  A scalar is one lambda."""
+    import numpy as np
+    lam = np.ascontiguousarray(np.atleast_1d(np.asarray(lambdas, dtype=np.float64)))
+    if lam.ndim != 1 or not 1 <= lam.size <= RELEVANCE_LAMBDAS_MAX:
+        raise ValueError(f"lambdas must be a scalar or a sequence of 1 to {RELEVANCE_LAMBDAS_MAX} values")
+    if not np.all(np.isfinite(lam)) or np.any(lam < 0.0) or np.any(lam > 1.0):
+        raise ValueError("every lambda must be finite and in [0, 1]")
+    return lam
 
 
 def topic_metric(metric) -> int:
@@ -186,6 +212,10 @@ SIGNATURES = {
     "lda_debug_cooc_chunk_tokens": (None, [C.c_int64]),
     "lda_topic_top_docs": (C.c_int32, [_vp, C.c_int32, C.c_double, C.c_int32, _vp, _vp, _vp]),
     "lda_debug_topic_docs_chunk_docs": (None, [C.c_int64]),
+    "lda_relevant_words": (C.c_int32, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lda_salient_words": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, _vp]),
+    "lda_word_rows": (C.c_int32, [_vp, C.c_int64, _vp, _vp, _vp]),
+    "lda_debug_relevance_slab_rows": (None, [C.c_int64]),
     "lda_topic_phrases": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp]),
     "lda_phrase_counts": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp, _vp]),

@@ -267,6 +267,15 @@ int64_t g_phrase_slots = 0;   // lda_debug_phrase_table_slots (0: sized from N)
 // keys (32 MiB at n = 64)
 constexpr int64_t TOP_WORDS_SLAB_ROWS = 256;
 constexpr int64_t TOP_WORDS_WAVES = 1024;
+// lda_relevant_words cuts the rows as lda_top_words does (at most
+// TOP_WORDS_WAVES waves of at most lda::RELEVANCE_LDS_BYTES of lists each);
+// lda_salient_words' slabs hold at least one LDS chunk of rows;
+// lda_word_rows' chunks hold WORD_ROWS_CELLS cells
+static_assert(LDA_RELEVANCE_LAMBDAS_MAX == 128, "the header states the limit");
+static_assert(LDA_SALIENT_WORDS_MAX == lda::SALIENT_MAX, "the header states the kernels' limit");
+static_assert(TOP_WORDS_WAVES <= lda::RELEVANCE_MAX_SLABS, "the merge holds every slab's head");
+constexpr int64_t WORD_ROWS_CELLS = int64_t(1) << 23;
+int64_t g_relevance_slab_rows = 0;   // lda_debug_relevance_slab_rows (0: the default cut)
 // lda_doc_counts / lda_doc_top_topics: int32 result cells (K or 2 m per
 // document) and documents per chunk
 constexpr int64_t READOUT_CELLS = int64_t(1) << 23;
@@ -405,6 +414,15 @@ struct lda_ctx {
   unsigned long long* td_bits = nullptr;
   int64_t *td_ids = nullptr, *td_out_ids = nullptr;
   size_t td_cap[6] = {};
+  // lda_relevant_words / lda_salient_words / lda_word_rows: grow-only scratch
+  // -- N [1], the word totals and their logs [V], the distinctiveness [V], the
+  // slab lists (keys, ids), the results of a pass (int32, int64, fp64), a
+  // chunk's word ids and rows
+  long long *rv_ntot = nullptr, *rv_tw = nullptr, *rv_out64 = nullptr;
+  double *rv_logtp = nullptr, *rv_dist = nullptr, *rv_outd = nullptr;
+  unsigned long long* rv_keys = nullptr;
+  int32_t *rv_ids = nullptr, *rv_out32 = nullptr, *rv_list = nullptr, *rv_rows = nullptr;
+  size_t rv_cap[11] = {};
   // lda_topic_phrases / lda_phrase_counts: grow-only scratch -- the table
   // (keys, counts), the selection's buckets, histogram and per-topic words,
   // the carried lists, the result, and a call's queries
@@ -569,6 +587,8 @@ struct lda_ctx {
                     (void*)dg_ids, (void*)dg_table, (void*)dg_out, (void*)dg_shares,
                     (void*)cc_moff, (void*)cc_mem, (void*)cc_words, (void*)cc_out, (void*)cc_off,
                     (void*)td_rows, (void*)td_cnts, (void*)td_out, (void*)td_bits, (void*)td_ids, (void*)td_out_ids,
+                    (void*)rv_ntot, (void*)rv_tw, (void*)rv_out64, (void*)rv_logtp, (void*)rv_dist, (void*)rv_outd,
+                    (void*)rv_keys, (void*)rv_ids, (void*)rv_out32, (void*)rv_list, (void*)rv_rows,
                     (void*)ph_keys, (void*)ph_u64, (void*)ph_sel_key, (void*)ph_cnts, (void*)ph_cand, (void*)ph_u32,
                     (void*)ph_hist, (void*)ph_sel_cnt, (void*)ph_out32, (void*)ph_q32, (void*)ph_out64, (void*)ph_q64,
                     (void*)perm, (void*)items, (void*)warm.range_doc, (void*)steady.range_doc,
@@ -2585,6 +2605,8 @@ hipError_t grow_bytes(void** ptr, size_t* cap, size_t bytes) {
   grow_bytes(reinterpret_cast<void**>(&(ptr)), &(c)->cc_cap[(slot)], (n) * sizeof(*(ptr)))
 #define td_need(c, ptr, n, slot) \
   grow_bytes(reinterpret_cast<void**>(&(ptr)), &(c)->td_cap[(slot)], (n) * sizeof(*(ptr)))
+#define rv_need(c, ptr, n, slot) \
+  grow_bytes(reinterpret_cast<void**>(&(ptr)), &(c)->rv_cap[(slot)], (n) * sizeof(*(ptr)))
 #define ph_need(c, ptr, n, slot) \
   grow_bytes(reinterpret_cast<void**>(&(ptr)), &(c)->ph_cap[(slot)], (n) * sizeof(*(ptr)))
 
@@ -2779,6 +2801,197 @@ lda_status lda_topic_top_docs(lda_ctx* c, int32_t n, double smoothing, int32_t m
   HIP_TRY(hipMemcpyAsync(doc_ids, a.out_ids, sizeof(int64_t) * cells, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(counts, a.out_counts, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(lengths, a.out_lengths, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LDA_OK;
+  });
+}
+
+void lda_debug_relevance_slab_rows(int64_t rows) { g_relevance_slab_rows = rows > 0 ? rows : 0; }
+
+namespace {
+// tw / logtp (and the distinctiveness, with dist) of every word, and N
+hipError_t word_totals(lda_ctx* c, lda::RelevanceArgs& a, bool dist) {
+  if (hipError_t e = rv_need(c, c->rv_ntot, (size_t)1, 0); e != hipSuccess) return e;
+  if (hipError_t e = rv_need(c, c->rv_tw, (size_t)c->V, 1); e != hipSuccess) return e;
+  if (hipError_t e = rv_need(c, c->rv_logtp, (size_t)c->V, 2); e != hipSuccess) return e;
+  if (dist)
+    if (hipError_t e = rv_need(c, c->rv_dist, (size_t)c->V, 3); e != hipSuccess) return e;
+  a.nw = c->nw;
+  a.nwsum = c->nwsum;
+  a.V = c->V;
+  a.K = c->K;
+  a.Kp = c->Kp;
+  a.beta = c->beta;
+  a.vbeta = (double)c->V * c->beta;
+  a.ntot = c->rv_ntot;
+  a.tw = c->rv_tw;
+  a.logtp = c->rv_logtp;
+  a.dist = dist ? c->rv_dist : nullptr;
+  return lda::launch_word_totals(a, c->stream);
+}
+}  // namespace
+
+lda_status lda_relevant_words(lda_ctx* c, int32_t n, int32_t L, const double* lambdas, int32_t* word_ids,
+                              int32_t* counts, int64_t* totals, double* logprob, double* loglift) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (n < 1 || n > LDA_TOP_WORDS_MAX) return fail(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_TOP_WORDS_MAX]");
+  if (L < 1 || L > LDA_RELEVANCE_LAMBDAS_MAX)
+    return fail(LDA_ERR_INVALID_ARG, "L must be in [1, LDA_RELEVANCE_LAMBDAS_MAX]");
+  if (!lambdas) return fail(LDA_ERR_INVALID_ARG, "null lambdas");
+  for (int32_t l = 0; l < L; ++l)
+    if (!std::isfinite(lambdas[l]) || !(lambdas[l] >= 0.0) || !(lambdas[l] <= 1.0))
+      return fail(LDA_ERR_INVALID_ARG, "every lambda must be finite and in [0, 1]");
+  if (!word_ids || !counts || !totals || !logprob || !loglift) return fail(LDA_ERR_INVALID_ARG, "null output");
+  if (c->pending) return fail(LDA_ERR_STATE, "relevant words with a pending delta: call lda_apply first");
+  const size_t cells = (size_t)c->K * (size_t)n;
+  if (c->V == 0) {
+    std::fill(word_ids, word_ids + cells * L, -1);
+    std::fill(counts, counts + cells * L, 0);
+    std::fill(totals, totals + cells * L, (int64_t)0);
+    std::fill(logprob, logprob + cells * L, 0.0);
+    std::fill(loglift, loglift + cells * L, 0.0);
+    return LDA_OK;
+  }
+  const int64_t G = c->Kp / 64;
+  int64_t slabs = std::min<int64_t>((c->V + TOP_WORDS_SLAB_ROWS - 1) / TOP_WORDS_SLAB_ROWS,
+                                    std::max<int64_t>(1, TOP_WORDS_WAVES / G));
+  int64_t slab_rows = (c->V + slabs - 1) / slabs;
+  if (g_relevance_slab_rows > 0)
+    slab_rows = std::max<int64_t>(g_relevance_slab_rows,
+                                  (c->V + lda::RELEVANCE_MAX_SLABS - 1) / lda::RELEVANCE_MAX_SLABS);
+  slabs = (c->V + slab_rows - 1) / slab_rows;
+  const int B = lda::relevance_batch(n);
+  const size_t entries = (size_t)(slabs * c->Kp) * (size_t)B * (size_t)n;
+  HIP_TRY(hipSetDevice(c->device));
+  lda::RelevanceArgs a{};
+  HIP_TRY(rv_need(c, c->rv_keys, entries, 4));
+  HIP_TRY(rv_need(c, c->rv_ids, entries, 5));
+  HIP_TRY(rv_need(c, c->rv_out32, 2 * B * cells, 6));
+  HIP_TRY(rv_need(c, c->rv_out64, B * cells, 7));
+  HIP_TRY(rv_need(c, c->rv_outd, 2 * B * cells, 8));
+  HIP_TRY(word_totals(c, a, false));
+  a.n = n;
+  a.slabs = (int32_t)slabs;
+  a.slab_rows = (int32_t)slab_rows;
+  a.batch = B;
+  a.keys = c->rv_keys;
+  a.ids = c->rv_ids;
+  a.out_ids = c->rv_out32;
+  a.out_counts = c->rv_out32 + B * cells;
+  a.out_totals = c->rv_out64;
+  a.out_logprob = c->rv_outd;
+  a.out_loglift = c->rv_outd + B * cells;
+  // the stream orders the passes: a pass's planes are copied out before the
+  // next pass's merge overwrites them
+  for (int32_t l0 = 0; l0 < L; l0 += B) {
+    const size_t nb = (size_t)std::min<int32_t>(B, L - l0), at = (size_t)l0 * cells;
+    for (int j = 0; j < B; ++j) a.m[j] = 1.0 - lambdas[std::min<int32_t>(l0 + j, L - 1)];
+    HIP_TRY(lda::launch_relevant_pass(a, c->stream));
+    HIP_TRY(hipMemcpyAsync(word_ids + at, a.out_ids, sizeof(int32_t) * nb * cells, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(counts + at, a.out_counts, sizeof(int32_t) * nb * cells, hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipMemcpyAsync(totals + at, a.out_totals, sizeof(int64_t) * nb * cells, hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipMemcpyAsync(logprob + at, a.out_logprob, sizeof(double) * nb * cells, hipMemcpyDeviceToHost,
+                           c->stream));
+    HIP_TRY(hipMemcpyAsync(loglift + at, a.out_loglift, sizeof(double) * nb * cells, hipMemcpyDeviceToHost,
+                           c->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LDA_OK;
+  });
+}
+
+lda_status lda_salient_words(lda_ctx* c, int32_t n, int32_t* word_ids, int64_t* totals, double* saliency,
+                             double* distinctiveness) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (n < 1 || n > LDA_SALIENT_WORDS_MAX) return fail(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_SALIENT_WORDS_MAX]");
+  if (!word_ids || !totals || !saliency || !distinctiveness) return fail(LDA_ERR_INVALID_ARG, "null output");
+  if (c->pending) return fail(LDA_ERR_STATE, "salient words with a pending delta: call lda_apply first");
+  if (c->V == 0) {
+    std::fill(word_ids, word_ids + n, -1);
+    std::fill(totals, totals + n, (int64_t)0);
+    std::fill(saliency, saliency + n, 0.0);
+    std::fill(distinctiveness, distinctiveness + n, 0.0);
+    return LDA_OK;
+  }
+  // slabs of at least one LDS chunk of rows, at most SALIENT_MAX_SLABS of them
+  const int64_t chunk = g_relevance_slab_rows > 0
+                            ? std::min<int64_t>(g_relevance_slab_rows, lda::SALIENT_CHUNK_ROWS)
+                            : lda::SALIENT_CHUNK_ROWS;
+  const int64_t min_rows = g_relevance_slab_rows > 0 ? 4 * chunk : chunk;
+  int64_t slabs = std::min<int64_t>((c->V + min_rows - 1) / min_rows, lda::SALIENT_MAX_SLABS);
+  const int64_t slab_rows = (c->V + slabs - 1) / slabs;
+  slabs = (c->V + slab_rows - 1) / slab_rows;
+  HIP_TRY(hipSetDevice(c->device));
+  lda::RelevanceArgs t{};
+  HIP_TRY(rv_need(c, c->rv_keys, (size_t)slabs * (size_t)n, 4));
+  HIP_TRY(rv_need(c, c->rv_ids, (size_t)slabs * (size_t)n, 5));
+  HIP_TRY(rv_need(c, c->rv_out32, (size_t)n, 6));
+  HIP_TRY(rv_need(c, c->rv_out64, (size_t)n, 7));
+  HIP_TRY(rv_need(c, c->rv_outd, 2 * (size_t)n, 8));
+  HIP_TRY(word_totals(c, t, true));
+  lda::SalientArgs a{};
+  a.ntot = c->rv_ntot;
+  a.tw = c->rv_tw;
+  a.dist = c->rv_dist;
+  a.V = c->V;
+  a.n = n;
+  a.slabs = (int32_t)slabs;
+  a.slab_rows = (int32_t)slab_rows;
+  a.chunk_rows = (int32_t)chunk;
+  a.keys = c->rv_keys;
+  a.ids = c->rv_ids;
+  a.out_ids = c->rv_out32;
+  a.out_totals = c->rv_out64;
+  a.out_saliency = c->rv_outd;
+  a.out_dist = c->rv_outd + n;
+  HIP_TRY(lda::launch_salient(a, c->stream));
+  HIP_TRY(hipMemcpyAsync(word_ids, a.out_ids, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(totals, a.out_totals, sizeof(int64_t) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(saliency, a.out_saliency, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(distinctiveness, a.out_dist, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost,
+                         c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LDA_OK;
+  });
+}
+
+lda_status lda_word_rows(lda_ctx* c, int64_t M, const int32_t* word_ids, int32_t* rows, int64_t* totals) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (M < 0) return fail(LDA_ERR_INVALID_ARG, "bad sizes");
+  if (M > 0 && !word_ids) return fail(LDA_ERR_INVALID_ARG, "null word list");
+  for (int64_t j = 0; j < M; ++j)
+    if (word_ids[j] < 0 || word_ids[j] >= c->V) return fail(LDA_ERR_INVALID_ARG, "word id out of range [0, V)");
+  if (M > 0 && (!rows || !totals)) return fail(LDA_ERR_INVALID_ARG, "null output");
+  if (c->pending) return fail(LDA_ERR_STATE, "word rows with a pending delta: call lda_apply first");
+  if (M == 0) return LDA_OK;
+  const int64_t Mc = std::min<int64_t>(M, std::max<int64_t>(1, WORD_ROWS_CELLS / c->K));
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(rv_need(c, c->rv_list, (size_t)Mc, 9));
+  HIP_TRY(rv_need(c, c->rv_rows, (size_t)(Mc * c->K), 10));
+  HIP_TRY(rv_need(c, c->rv_out64, (size_t)Mc, 7));
+  lda::WordRowsArgs a{};
+  a.nw = c->nw;
+  a.ids = c->rv_list;
+  a.K = c->K;
+  a.Kp = c->Kp;
+  a.rows = c->rv_rows;
+  a.totals = c->rv_out64;
+  // the stream orders the chunks: a chunk's rows are copied out before the
+  // next chunk's ids arrive
+  for (int64_t j0 = 0; j0 < M; j0 += Mc) {
+    a.M = std::min<int64_t>(Mc, M - j0);
+    HIP_TRY(hipMemcpyAsync(c->rv_list, word_ids + j0, sizeof(int32_t) * (size_t)a.M, hipMemcpyHostToDevice,
+                           c->stream));
+    HIP_TRY(lda::launch_word_rows(a, c->stream));
+    HIP_TRY(hipMemcpyAsync(rows + (size_t)j0 * c->K, a.rows, sizeof(int32_t) * (size_t)(a.M * c->K),
+                           hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(totals + j0, a.totals, sizeof(int64_t) * (size_t)a.M, hipMemcpyDeviceToHost, c->stream));
+  }
   HIP_TRY(hipStreamSynchronize(c->stream));
   return LDA_OK;
   });

@@ -596,4 +596,83 @@ hipError_t launch_phrase_select(const PhraseArgs& a, int blocks, hipStream_t st)
 hipError_t launch_phrase_gather(const PhraseArgs& a, hipStream_t st);
 hipError_t launch_phrase_lookup(const PhraseArgs& a, hipStream_t st);
 
+// ---- lda_relevant_words / lda_salient_words / lda_word_rows
+// k_word_totals: one wave per word row, tw[w] = the row's integer sum over
+// k < K, logtp[w] = log((double) tw / (double) N) (0.0 where tw = 0) and, with
+// dist non-null, the word's distinctiveness; N = nwsum[0] + ... + nwsum[K-1]
+// comes from k_token_total (ntot[0]).
+// lda_relevant_words: a pass handles `batch` (1, 2, 4 or 8) lambdas.  Stage 1
+// (k_relevant_slab) keeps, per (slab of rows, topic, lambda of the pass), the
+// slab's best n (key, word) as a descending list,
+// keys / ids[((((slab * G + group) * batch + j) * n + i) * 64 + lane]
+// (G = Kp / 64, key 0 = an empty slot); stage 2 (k_relevant_merge, grid
+// (K, batch)) merges a topic's slab lists and writes plane j of the pass:
+// out_*[(j * K + k) * n + i].  slabs <= RELEVANCE_MAX_SLABS.
+constexpr int RELEVANCE_MAX_SLABS = 1024;
+constexpr int RELEVANCE_BATCH_MAX = 8;
+constexpr size_t RELEVANCE_LDS_BYTES = 64 * 1024;
+constexpr int RELEVANCE_ENTRY_BYTES = 12;   // the key's 8 and the word id's 4
+// the lambdas a wave keeps at once: the largest of 8, 4, 2, 1 whose lists
+// (n x 64 entries each) fit RELEVANCE_LDS_BYTES -- 8 up to n = 10, 4 up to
+// n = 21, 2 up to n = 42, else 1
+constexpr int relevance_batch(int n) {
+  int b = RELEVANCE_BATCH_MAX;
+  while (b > 1 && (size_t)b * (size_t)n * 64 * RELEVANCE_ENTRY_BYTES > RELEVANCE_LDS_BYTES) b >>= 1;
+  return b;
+}
+struct RelevanceArgs {
+  const int32_t* nw;             // [V * Kp]
+  const int32_t* nwsum;          // [Kp]
+  int32_t V, K, Kp, n;
+  int32_t slabs, slab_rows;      // slab s holds rows [s * slab_rows, min(V, (s + 1) * slab_rows))
+  int32_t batch;
+  double beta, vbeta;
+  double m[RELEVANCE_BATCH_MAX]; // 1.0 - lambda of the pass's lists
+  long long* ntot;               // [1]
+  long long* tw;                 // [V]
+  double* logtp;                 // [V]
+  double* dist;                  // [V] or null
+  unsigned long long* keys;      // [slabs * Kp * batch * n]
+  int32_t* ids;                  // [slabs * Kp * batch * n]
+  int32_t* out_ids;              // [batch * K * n]
+  int32_t* out_counts;           // [batch * K * n]
+  long long* out_totals;         // [batch * K * n]
+  double* out_logprob;           // [batch * K * n]
+  double* out_loglift;           // [batch * K * n]
+};
+hipError_t launch_word_totals(const RelevanceArgs& a, hipStream_t st);
+hipError_t launch_relevant_pass(const RelevanceArgs& a, hipStream_t st);
+// lda_salient_words: k_salient_slab, one wave per slab of rows, keeps the
+// slab's best n (saliency key, word) in keys / ids[slab * n + i], descending;
+// k_salient_merge (one wave) merges them into out_*[n].
+// slabs <= SALIENT_MAX_SLABS, n <= SALIENT_MAX.
+constexpr int SALIENT_MAX = 256;
+constexpr int SALIENT_MAX_SLABS = 1024;
+constexpr int SALIENT_CHUNK_ROWS = 1024;
+struct SalientArgs {
+  const long long* ntot;         // [1]
+  const long long* tw;           // [V]
+  const double* dist;            // [V]
+  int32_t V, n, slabs, slab_rows;
+  int32_t chunk_rows;            // rows per LDS chunk, 1 .. SALIENT_CHUNK_ROWS
+  unsigned long long* keys;      // [slabs * n]
+  int32_t* ids;                  // [slabs * n]
+  int32_t* out_ids;              // [n]
+  long long* out_totals;         // [n]
+  double* out_saliency;          // [n]
+  double* out_dist;              // [n]
+};
+hipError_t launch_salient(const SalientArgs& a, hipStream_t st);
+// lda_word_rows: k_word_rows, one wave per listed word: its unpadded row and
+// its total.
+struct WordRowsArgs {
+  const int32_t* nw;             // [V * Kp]
+  const int32_t* ids;            // [M]
+  int64_t M;
+  int32_t K, Kp;
+  int32_t* rows;                 // [M * K]
+  long long* totals;             // [M]
+};
+hipError_t launch_word_rows(const WordRowsArgs& a, hipStream_t st);
+
 }  // namespace lda

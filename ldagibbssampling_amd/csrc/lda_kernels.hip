@@ -5820,4 +5820,395 @@ hipError_t launch_phrase_lookup(const PhraseArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// ---- lda_relevant_words / lda_salient_words / lda_word_rows
+
+// An fp64 value (not NaN) as a uint64 whose unsigned order is the value's:
+// every bit of a negative value flipped, else the sign bit set.  -0.0 is
+// taken as 0.0.  No value maps to 0, which marks an empty slot.
+__device__ __forceinline__ unsigned long long ordered_bits(double v) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v + 0.0);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+// The wave's best (key, id): the larger key, equal keys by the smaller id
+// (every lane gets it).
+__device__ __forceinline__ void wave_best_pair(unsigned long long& wb, int32_t& wi) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t bh = (uint32_t)__shfl_xor((int)(wb >> 32), o), bl = (uint32_t)__shfl_xor((int)(uint32_t)wb, o);
+    const int32_t oi = __shfl_xor(wi, o);
+    const unsigned long long ob = ((unsigned long long)bh << 32) | bl;
+    if (ob > wb || (ob == wb && oi < wi)) {
+      wb = ob;
+      wi = oi;
+    }
+  }
+}
+
+// N = nwsum[0] + ... + nwsum[K - 1] (one wave; integers).
+__global__ __launch_bounds__(64) void k_token_total(const RelevanceArgs a) {
+  long long t = 0;
+  for (int k = threadIdx.x; k < a.K; k += 64) t += a.nwsum[k];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+  if (threadIdx.x == 0) a.ntot[0] = t;
+}
+
+// One wave per word row: tw = the row's integer sum over k < K,
+// logtp = log((double) tw / (double) N) (0.0 for a word without tokens, which
+// is nobody's candidate).  With dist: the word's distinctiveness, the sum over
+// k < K with nw[w, k] > 0 of q log(q / p_k), q = (double) nw / (double) tw,
+// p_k = (double) nwsum[k] / (double) N -- lane l adds k = l, l + 64, ... in
+// ascending order from 0.0, then the lanes combine in the xor butterfly 32,
+// 16, 8, 4, 2, 1 (wave_sum_d), as k_word_stats adds its shares: a function of
+// the row, nwsum and K alone.
+__global__ __launch_bounds__(256) void k_word_totals(const RelevanceArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (w >= a.V) return;
+  const int32_t* __restrict__ row = a.nw + (size_t)w * a.Kp;
+  long long tot = 0;
+  for (int k = lane; k < a.K; k += 64) tot += row[k];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
+  const double N = (double)a.ntot[0];
+  double d = 0.0;
+  if (a.dist && tot > 0) {
+    const double t = (double)tot;
+    for (int k = lane; k < a.K; k += 64) {
+      const int32_t c = row[k];
+      if (c > 0) {
+        const double q = (double)c / t, p = (double)a.nwsum[k] / N;
+        d += q * log(q / p);
+      }
+    }
+    d = wave_sum_d(d);
+  }
+  if (lane == 0) {
+    a.tw[w] = tot;
+    a.logtp[w] = tot > 0 ? log((double)tot / N) : 0.0;
+    if (a.dist) a.dist[w] = d;
+  }
+}
+
+// lda_relevant_words, stage 1: one wave per (slab of rows, group of 64
+// topics), lane l owning topic group * 64 + l, as k_top_words_slab cuts the
+// table.  A cell with nw > 0 costs one division and one log (logprob) and a
+// wave-uniform load of the row's logtp; each of the pass's B lambdas then adds
+// key = logprob - m_j * logtp (one rounding per operation), its ordered bits
+// and a compare against that list's threshold thr[j], the smallest kept key of
+// a full list.  The lane's B lists, keys and word ids, are its own LDS
+// columns ((j * n + i) * 64 + lane: no lane reads another's, no fence).  Rows
+// arrive in ascending id, so the strict compares keep the smaller id first
+// among equal keys and drop an equal key at a full list's end; len spares a
+// list that is not yet full the shift through its empty tail.  A key is a
+// function of (nw[w, k], nwsum[k], tw[w], N, beta, V, lambda) alone: not of
+// B, of j or of the slab.
+template <int B>
+__global__ __launch_bounds__(64) void k_relevant_slab(const RelevanceArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long rl_lds[];   // keys [B][n][64], then ids
+  const int lane = threadIdx.x, n = a.n;
+  unsigned long long* lk = rl_lds + lane;
+  int32_t* li = reinterpret_cast<int32_t*>(rl_lds + (size_t)B * n * 64) + lane;
+  const int s = blockIdx.x, g = blockIdx.y, G = a.Kp >> 6;
+  for (int i = 0; i < B * n; ++i) {
+    lk[i * 64] = 0;
+    li[i * 64] = -1;
+  }
+  unsigned long long thr[B];
+  int len[B];
+  double m[B];
+#pragma unroll
+  for (int j = 0; j < B; ++j) {
+    thr[j] = 0;
+    len[j] = 0;
+    m[j] = a.m[j];
+  }
+  const int32_t* __restrict__ col = a.nw + (size_t)g * 64 + lane;
+  const double* __restrict__ logtp = a.logtp;
+  const double denom = (double)a.nwsum[g * 64 + lane] + a.vbeta;
+  const int64_t w0 = (int64_t)s * a.slab_rows, w1 = min((int64_t)a.V, w0 + a.slab_rows);
+  for (int64_t w = w0; w < w1; w += 8) {
+    int32_t c[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) c[u] = w + u < w1 ? col[(size_t)(w + u) * a.Kp] : 0;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      if (c[u] <= 0) continue;
+      const double lp = log(((double)c[u] + a.beta) / denom), lt = logtp[w + u];
+#pragma unroll
+      for (int j = 0; j < B; ++j) {
+        const unsigned long long key = ordered_bits(lp - m[j] * lt);
+        if (key > thr[j]) {
+          unsigned long long* kj = lk + (size_t)j * n * 64;
+          int32_t* ij = li + (size_t)j * n * 64;
+          int i = min(len[j], n - 1);
+          while (i > 0) {
+            const unsigned long long prev = kj[(i - 1) * 64];
+            if (prev >= key) break;
+            kj[i * 64] = prev;
+            ij[i * 64] = ij[(i - 1) * 64];
+            --i;
+          }
+          kj[i * 64] = key;
+          ij[i * 64] = (int32_t)(w + u);
+          len[j] = min(len[j] + 1, n);
+          thr[j] = kj[(n - 1) * 64];
+        }
+      }
+    }
+  }
+  const size_t base = ((size_t)s * G + g) * B * n * 64 + lane;
+  for (int i = 0; i < B * n; ++i) {
+    a.keys[base + (size_t)i * 64] = lk[i * 64];
+    a.ids[base + (size_t)i * 64] = li[i * 64];
+  }
+}
+
+// lda_relevant_words, stage 2: one wave per (topic k < K, lambda j of the
+// pass) merges the topic's slab lists as k_topic_docs_merge does, lane l
+// holding the heads of slabs l, l + 64, ...  The arg-max is over (key, then
+// smaller word id): the pair is unique per topic, so the winner names its
+// slab, whose owner writes the slot -- count, tw, logprob formed exactly as
+// stage 1 forms it, loglift = logprob - logtp -- and steps the list.  An
+// exhausted merge fills -1 / 0 / 0 / 0.0 / 0.0.
+__global__ __launch_bounds__(64) void k_relevant_merge(const RelevanceArgs a) {
+  __shared__ unsigned long long head[RELEVANCE_MAX_SLABS];
+  __shared__ int32_t hid[RELEVANCE_MAX_SLABS];
+  __shared__ int32_t ptr[RELEVANCE_MAX_SLABS];
+  const int lane = threadIdx.x, n = a.n, k = blockIdx.x, j = blockIdx.y, g = k >> 6, kl = k & 63, G = a.Kp >> 6;
+  auto at = [&](int s, int i) { return ((((size_t)s * G + g) * a.batch + j) * n + i) * 64 + kl; };
+  for (int s = lane; s < a.slabs; s += 64) {
+    const unsigned long long b = a.keys[at(s, 0)];
+    head[s] = b;
+    hid[s] = b ? a.ids[at(s, 0)] : INT32_MAX;
+    ptr[s] = 0;
+  }
+  const double denom = (double)a.nwsum[k] + a.vbeta;
+  for (int i = 0; i < n; ++i) {
+    unsigned long long best = 0;
+    int32_t bid = INT32_MAX;
+    int bs = -1;
+    for (int s = lane; s < a.slabs; s += 64) {
+      const unsigned long long hb = head[s];
+      const int32_t id = hid[s];
+      if (hb > best || (hb == best && id < bid)) {
+        best = hb;
+        bid = id;
+        bs = s;
+      }
+    }
+    unsigned long long wb = best;
+    int32_t wi = bid;
+    wave_best_pair(wb, wi);
+    const size_t o = ((size_t)j * a.K + k) * n + i;
+    if (wb == 0) {
+      if (lane == 0) {
+        a.out_ids[o] = -1;
+        a.out_counts[o] = 0;
+        a.out_totals[o] = 0;
+        a.out_logprob[o] = 0.0;
+        a.out_loglift[o] = 0.0;
+      }
+    } else if (best == wb && bid == wi) {   // this lane owns the winner's slab
+      const int32_t c = a.nw[(size_t)wi * a.Kp + k];
+      const double lp = log(((double)c + a.beta) / denom);
+      a.out_ids[o] = wi;
+      a.out_counts[o] = c;
+      a.out_totals[o] = a.tw[wi];
+      a.out_logprob[o] = lp;
+      a.out_loglift[o] = lp - a.logtp[wi];
+      const int p = ++ptr[bs];
+      const unsigned long long nb = p < n ? a.keys[at(bs, p)] : 0ull;
+      head[bs] = nb;
+      hid[bs] = nb ? a.ids[at(bs, p)] : INT32_MAX;
+    }
+  }
+}
+
+// saliency = ((double) tw / (double) N) * distinctiveness, as a key
+__device__ __forceinline__ double saliency_of(long long tw, double N, double dist) { return ((double)tw / N) * dist; }
+
+// lda_salient_words, stage 1: one wave per slab of rows.  The slab goes
+// through LDS in chunks of chunk_rows rows placed behind the best n
+// kept so far (key 0 = a word without tokens, no candidate); n rounds of a
+// wave-wide arg-max over (key, then smaller id) -- lane l scanning entries l,
+// l + 64, ..., the winner's owner clearing it -- select the best n of both,
+// which move to the front for the next chunk.  The result is the best n of
+// the slab's rows whatever the chunk size: (key, id) is unique.
+__global__ __launch_bounds__(64) void k_salient_slab(const SalientArgs a) {
+  __shared__ unsigned long long ck[SALIENT_MAX + SALIENT_CHUNK_ROWS];
+  __shared__ int32_t ci[SALIENT_MAX + SALIENT_CHUNK_ROWS];
+  __shared__ unsigned long long ok[SALIENT_MAX];
+  __shared__ int32_t oi[SALIENT_MAX];
+  const int lane = threadIdx.x, n = a.n, s = blockIdx.x;
+  const double N = (double)a.ntot[0];
+  const int64_t w0 = (int64_t)s * a.slab_rows, w1 = min((int64_t)a.V, w0 + a.slab_rows);
+  int kept = 0;
+  for (int64_t c0 = w0; c0 < w1; c0 += a.chunk_rows) {
+    const int m = (int)min((int64_t)a.chunk_rows, w1 - c0);
+    for (int r = lane; r < m; r += 64) {
+      const int64_t w = c0 + r;
+      const long long t = a.tw[w];
+      ck[kept + r] = t > 0 ? ordered_bits(saliency_of(t, N, a.dist[w])) : 0ull;
+      ci[kept + r] = (int32_t)w;
+    }
+    wave_lds_fence();
+    const int total = kept + m;
+    int found = 0;
+    for (int i = 0; i < n; ++i) {
+      unsigned long long best = 0;
+      int32_t bid = INT32_MAX;
+      int bpos = -1;
+      for (int r = lane; r < total; r += 64) {
+        const unsigned long long kb = ck[r];
+        const int32_t id = ci[r];
+        if (kb > best || (kb == best && kb != 0 && id < bid)) {
+          best = kb;
+          bid = id;
+          bpos = r;
+        }
+      }
+      unsigned long long wb = best;
+      int32_t wi = bid;
+      wave_best_pair(wb, wi);
+      if (wb == 0) break;
+      if (best == wb && bid == wi) {
+        ok[i] = wb;
+        oi[i] = wi;
+        ck[bpos] = 0;
+      }
+      ++found;
+    }
+    wave_lds_fence();
+    for (int r = lane; r < found; r += 64) {
+      ck[r] = ok[r];
+      ci[r] = oi[r];
+    }
+    wave_lds_fence();
+    kept = found;
+  }
+  for (int i = lane; i < n; i += 64) {
+    a.keys[(size_t)s * n + i] = i < kept ? ck[i] : 0ull;
+    a.ids[(size_t)s * n + i] = i < kept ? ci[i] : -1;
+  }
+}
+
+// lda_salient_words, stage 2: one wave merges the slabs' lists as
+// k_relevant_merge does; the winner's owner writes id, tw, the saliency
+// (formed as stage 1 forms it) and the distinctiveness.  An exhausted merge
+// fills -1 / 0 / 0.0 / 0.0.
+__global__ __launch_bounds__(64) void k_salient_merge(const SalientArgs a) {
+  __shared__ unsigned long long head[SALIENT_MAX_SLABS];
+  __shared__ int32_t hid[SALIENT_MAX_SLABS];
+  __shared__ int32_t ptr[SALIENT_MAX_SLABS];
+  const int lane = threadIdx.x, n = a.n;
+  const double N = (double)a.ntot[0];
+  for (int s = lane; s < a.slabs; s += 64) {
+    const unsigned long long b = a.keys[(size_t)s * n];
+    head[s] = b;
+    hid[s] = b ? a.ids[(size_t)s * n] : INT32_MAX;
+    ptr[s] = 0;
+  }
+  for (int i = 0; i < n; ++i) {
+    unsigned long long best = 0;
+    int32_t bid = INT32_MAX;
+    int bs = -1;
+    for (int s = lane; s < a.slabs; s += 64) {
+      const unsigned long long hb = head[s];
+      const int32_t id = hid[s];
+      if (hb > best || (hb == best && id < bid)) {
+        best = hb;
+        bid = id;
+        bs = s;
+      }
+    }
+    unsigned long long wb = best;
+    int32_t wi = bid;
+    wave_best_pair(wb, wi);
+    if (wb == 0) {
+      if (lane == 0) {
+        a.out_ids[i] = -1;
+        a.out_totals[i] = 0;
+        a.out_saliency[i] = 0.0;
+        a.out_dist[i] = 0.0;
+      }
+    } else if (best == wb && bid == wi) {   // this lane owns the winner's slab
+      const long long t = a.tw[wi];
+      const double d = a.dist[wi];
+      a.out_ids[i] = wi;
+      a.out_totals[i] = t;
+      a.out_saliency[i] = saliency_of(t, N, d);
+      a.out_dist[i] = d;
+      const int p = ++ptr[bs];
+      const unsigned long long nb = p < n ? a.keys[(size_t)bs * n + p] : 0ull;
+      head[bs] = nb;
+      hid[bs] = nb ? a.ids[(size_t)bs * n + p] : INT32_MAX;
+    }
+  }
+}
+
+// lda_word_rows: one wave per listed word copies the K cells of its row and
+// sums them.
+__global__ __launch_bounds__(256) void k_word_rows(const WordRowsArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= a.M) return;
+  const int32_t* __restrict__ row = a.nw + (size_t)a.ids[j] * a.Kp;
+  long long tot = 0;
+  for (int k = lane; k < a.K; k += 64) {
+    const int32_t c = row[k];
+    a.rows[j * a.K + k] = c;
+    tot += c;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
+  if (lane == 0) a.totals[j] = tot;
+}
+
+hipError_t launch_word_totals(const RelevanceArgs& a, hipStream_t st) {
+  if (a.V < 1 || a.K < 1 || a.K > a.Kp || a.Kp % 64 != 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_token_total, dim3(1), dim3(64), 0, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_word_totals, dim3((unsigned)(((int64_t)a.V + 3) / 4)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_relevant_pass(const RelevanceArgs& a, hipStream_t st) {
+  if (a.n < 1 || a.n > 64 || a.batch != relevance_batch(a.n) || a.slabs < 1 || a.slabs > RELEVANCE_MAX_SLABS ||
+      a.V < 1 || a.slab_rows < 1 || (int64_t)a.slabs * a.slab_rows < a.V || a.K < 1 || a.K > a.Kp || a.Kp % 64 != 0)
+    return hipErrorInvalidValue;
+  // n x 64 x 12 bytes of LDS per list: at most RELEVANCE_LDS_BYTES per one-wave block
+  const size_t lds = (size_t)a.batch * a.n * 64 * RELEVANCE_ENTRY_BYTES;
+  const dim3 grid(a.slabs, a.Kp / 64);
+  switch (a.batch) {
+    case 8: hipLaunchKernelGGL(k_relevant_slab<8>, grid, dim3(64), lds, st, a); break;
+    case 4: hipLaunchKernelGGL(k_relevant_slab<4>, grid, dim3(64), lds, st, a); break;
+    case 2: hipLaunchKernelGGL(k_relevant_slab<2>, grid, dim3(64), lds, st, a); break;
+    default: hipLaunchKernelGGL(k_relevant_slab<1>, grid, dim3(64), lds, st, a); break;
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_relevant_merge, dim3(a.K, a.batch), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_salient(const SalientArgs& a, hipStream_t st) {
+  if (a.n < 1 || a.n > SALIENT_MAX || a.slabs < 1 || a.slabs > SALIENT_MAX_SLABS || a.V < 1 || a.slab_rows < 1 ||
+      (int64_t)a.slabs * a.slab_rows < a.V || a.chunk_rows < 1 || a.chunk_rows > SALIENT_CHUNK_ROWS)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_salient_slab, dim3(a.slabs), dim3(64), 0, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_salient_merge, dim3(1), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_word_rows(const WordRowsArgs& a, hipStream_t st) {
+  if (a.M < 1 || a.M > (int64_t(1) << 31) || a.K < 1 || a.K > a.Kp) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_word_rows, dim3((unsigned)((a.M + 3) / 4)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
 }  // namespace lda

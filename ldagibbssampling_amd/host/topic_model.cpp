@@ -958,6 +958,77 @@ void ParallelTopicModel::topWords(int32_t n, int32_t* word_ids, int32_t* counts)
 }
 
 namespace {
+// lda_relevant_words' argument checks, in its order, before any shard is built
+void checkRelevance(int32_t n, int32_t L, const double* lambdas) {
+  if (n < 1 || n > LDA_TOP_WORDS_MAX) raise(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_TOP_WORDS_MAX]");
+  if (L < 1 || L > LDA_RELEVANCE_LAMBDAS_MAX) raise(LDA_ERR_INVALID_ARG, "L must be in [1, LDA_RELEVANCE_LAMBDAS_MAX]");
+  if (!lambdas) raise(LDA_ERR_INVALID_ARG, "null lambdas");
+  for (int32_t l = 0; l < L; ++l)
+    if (!std::isfinite(lambdas[l]) || !(lambdas[l] >= 0.0) || !(lambdas[l] <= 1.0))
+      raise(LDA_ERR_INVALID_ARG, "every lambda must be finite and in [0, 1]");
+}
+}  // namespace
+
+void ParallelTopicModel::relevantWords(int32_t n, int32_t L, const double* lambdas, int32_t* word_ids, int32_t* counts,
+                                       int64_t* totals, double* logprob, double* loglift) {
+  checkRelevance(n, L, lambdas);
+  if (!word_ids || !counts || !totals || !logprob || !loglift) raise(LDA_ERR_INVALID_ARG, "null output");
+  ensureShards();
+  check(lda_relevant_words(shards_->ctx[0], n, L, lambdas, word_ids, counts, totals, logprob, loglift),
+        "lda_relevant_words");
+}
+
+void ParallelTopicModel::salientWords(int32_t n, int32_t* word_ids, int64_t* totals, double* saliency,
+                                      double* distinctiveness) {
+  if (n < 1 || n > LDA_SALIENT_WORDS_MAX) raise(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_SALIENT_WORDS_MAX]");
+  if (!word_ids || !totals || !saliency || !distinctiveness) raise(LDA_ERR_INVALID_ARG, "null output");
+  ensureShards();
+  check(lda_salient_words(shards_->ctx[0], n, word_ids, totals, saliency, distinctiveness), "lda_salient_words");
+}
+
+void ParallelTopicModel::wordRows(int64_t M, const int32_t* word_ids, int32_t* rows, int64_t* totals) {
+  if (M < 0) raise(LDA_ERR_INVALID_ARG, "bad sizes");
+  if (M > 0 && !word_ids) raise(LDA_ERR_INVALID_ARG, "null word list");
+  for (int64_t j = 0; j < M; ++j)
+    if (word_ids[j] < 0 || word_ids[j] >= numTypes()) raise(LDA_ERR_INVALID_ARG, "word id out of range [0, V)");
+  if (M == 0) return;
+  if (!rows || !totals) raise(LDA_ERR_INVALID_ARG, "null output");
+  ensureShards();
+  check(lda_word_rows(shards_->ctx[0], M, word_ids, rows, totals), "lda_word_rows");
+}
+
+double relevanceOf(double lambda, double logprob, double loglift) {
+  return logprob - (1.0 - lambda) * (logprob - loglift);
+}
+
+std::string relevantWordsFormat(int32_t K, int32_t n, double lambda, const int32_t* word_ids, const int32_t* counts,
+                                const int64_t* totals, const double* logprob, const double* loglift,
+                                const std::function<std::string(int32_t)>& name) {
+  std::string out = "#topic rank word count total relevance logprob loglift\n";
+  for (int32_t k = 0; k < K; ++k)
+    for (int32_t i = 0; i < n; ++i) {
+      const size_t at = (size_t)k * n + i;
+      if (word_ids[at] < 0) break;
+      out += std::to_string(k) + " " + std::to_string(i) + " " + name(word_ids[at]) + " " + std::to_string(counts[at]) +
+             " " + std::to_string(totals[at]) + " " + java_double(relevanceOf(lambda, logprob[at], loglift[at])) + " " +
+             java_double(logprob[at]) + " " + java_double(loglift[at]) + "\n";
+    }
+  return out;
+}
+
+std::string ParallelTopicModel::relevantWordsText(int32_t n, double lambda) {
+  checkRelevance(n, 1, &lambda);
+  const size_t cells = (size_t)K_ * (size_t)n;
+  std::vector<int32_t> ids(cells), cnt(cells);
+  std::vector<int64_t> tot(cells);
+  std::vector<double> lp(cells), ll(cells);
+  relevantWords(n, 1, &lambda, ids.data(), cnt.data(), tot.data(), lp.data(), ll.data());
+  return relevantWordsFormat(K_, n, lambda, ids.data(), cnt.data(), tot.data(), lp.data(), ll.data(), [&](int32_t w) {
+    return alphabet_.empty() ? std::to_string(w) : alphabet_[(size_t)w];
+  });
+}
+
+namespace {
 // the arguments of topicDistances / nearestTopics (n null: no n), in
 // lda_topic_distances' order, before any shard is built
 void checkTopicPair(const ParallelTopicModel& m, const ParallelTopicModel* other, int32_t metric, const int32_t* n,
@@ -2444,6 +2515,55 @@ lda_status ldatm_topic_documents_format(int32_t K, int32_t n, double smoothing, 
   lda_status st = guard([&] {
     s = lda_host::topicDocumentsFormat(K, n, smoothing, doc_ids, counts, lengths, [&](int64_t d) {
       return d < num_names && names[d] ? std::string(names[d]) : std::string("null-source");
+    });
+  });
+  return st ? st : copy_text(s, buf, cap, len);
+}
+
+lda_status ldatm_relevant_words(ldatm* m, int32_t n, int32_t L, const double* lambdas, int32_t* word_ids,
+                                int32_t* counts, int64_t* totals, double* logprob, double* loglift) {
+  TM_CHECK(m);
+  return guard([&] { m->model.relevantWords(n, L, lambdas, word_ids, counts, totals, logprob, loglift); });
+}
+
+lda_status ldatm_salient_words(ldatm* m, int32_t n, int32_t* word_ids, int64_t* totals, double* saliency,
+                               double* distinctiveness) {
+  TM_CHECK(m);
+  return guard([&] { m->model.salientWords(n, word_ids, totals, saliency, distinctiveness); });
+}
+
+lda_status ldatm_word_rows(ldatm* m, int64_t M, const int32_t* word_ids, int32_t* rows, int64_t* totals) {
+  TM_CHECK(m);
+  return guard([&] { m->model.wordRows(M, word_ids, rows, totals); });
+}
+
+lda_status ldatm_relevant_words_text(ldatm* m, int32_t n, double lambda, char* buf, size_t cap, size_t* len) {
+  TM_CHECK(m);
+  std::string s;
+  lda_status st = guard([&] { s = m->model.relevantWordsText(n, lambda); });
+  return st ? st : copy_text(s, buf, cap, len);
+}
+
+lda_status ldatm_print_relevant_words(ldatm* m, const char* path, int32_t n, double lambda) {
+  TM_CHECK(m);
+  std::string s;
+  lda_status st = guard([&] { s = m->model.relevantWordsText(n, lambda); });
+  return st ? st : write_file(path, s);
+}
+
+lda_status ldatm_relevant_words_format(int32_t K, int32_t n, double lambda, const int32_t* word_ids,
+                                       const int32_t* counts, const int64_t* totals, const double* logprob,
+                                       const double* loglift, const char* const* names, int64_t num_names, char* buf,
+                                       size_t cap, size_t* len) {
+  if (K < 1 || n < 1 || !std::isfinite(lambda) || !(lambda >= 0.0) || !(lambda <= 1.0) || !word_ids || !counts ||
+      !totals || !logprob || !loglift || num_names < 0 || (num_names > 0 && !names)) {
+    g_tm_error = "bad argument";
+    return LDA_ERR_INVALID_ARG;
+  }
+  std::string s;
+  lda_status st = guard([&] {
+    s = lda_host::relevantWordsFormat(K, n, lambda, word_ids, counts, totals, logprob, loglift, [&](int32_t w) {
+      return w >= 0 && w < num_names && names[w] ? std::string(names[w]) : std::to_string(w);
     });
   });
   return st ? st : copy_text(s, buf, cap, len);

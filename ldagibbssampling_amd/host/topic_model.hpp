@@ -48,6 +48,13 @@ double topicDocWeight(int32_t K, double smoothing, int32_t count, int32_t length
 std::string topicDocumentsFormat(int32_t K, int32_t n, double smoothing, const int64_t* doc_ids, const int32_t* counts,
                                  const int32_t* lengths, const std::function<std::string(int64_t)>& name);
 
+// ldatm_relevant_words_format's relevance, logprob - (1 - lambda) (logprob -
+// loglift), and its text from K x n lists (host only, no device)
+double relevanceOf(double lambda, double logprob, double loglift);
+std::string relevantWordsFormat(int32_t K, int32_t n, double lambda, const int32_t* word_ids, const int32_t* counts,
+                                const int64_t* totals, const double* logprob, const double* loglift,
+                                const std::function<std::string(int32_t)>& name);
+
 // lda_topic_phrases over several shards: B_k, the sum over
 // the shards of the count of the shard's last (LDA_PHRASES_MAX-th) listed
 // phrase of topic k (0 where the list is not full), bounds the total of every
@@ -150,6 +157,18 @@ class ParallelTopicModel {
   // arguments are checked before any shard is built.
   void topicTopDocs(int32_t n, double smoothing, int32_t min_tokens, int64_t* doc_ids, int32_t* counts,
                     int32_t* lengths);
+
+  // lda_relevant_words / lda_salient_words / lda_word_rows on shard 0
+  // (every shard holds the same global counts).  The arguments
+  // are checked before any shard is built.  Planes [L*K*n]; lists [n]; rows
+  // [M*K] and totals [M]
+  void relevantWords(int32_t n, int32_t L, const double* lambdas, int32_t* word_ids, int32_t* counts,
+                     int64_t* totals, double* logprob, double* loglift);
+  void salientWords(int32_t n, int32_t* word_ids, int64_t* totals, double* saliency, double* distinctiveness);
+  void wordRows(int64_t M, const int32_t* word_ids, int32_t* rows, int64_t* totals);
+  // relevantWords(n, one lambda) as text: "topic rank word count total
+  // relevance logprob loglift" per topic and rank
+  std::string relevantWordsText(int32_t n, double lambda);
 
   // lda_topic_phrases.  One shard: passed through, proven[k]
   // = n.  Several: every shard's best LDA_PHRASES_MAX per topic united by

@@ -407,6 +407,58 @@ class GibbsSampler:
         capi.check(self._L.lda_top_words(self._h, n, ids.ctypes.data, cnt.ctypes.data), "lda_top_words")
         return ids, cnt
 
+    def relevant_words(self, n: int, lambdas=0.6):
+        """lda_relevant_words: for each lambda (a scalar or a sequence of up to
+        RELEVANCE_LAMBDAS_MAX values in [0, 1]) and topic, the n words with
+        nw[w, k] > 0 of largest relevance lambda logprob + (1 - lambda) loglift
+        (Sievert & Shirley 2014), equal keys by ascending word id, selected on
+        the device.  Returns (word_ids, counts int32, totals int64, logprob,
+        loglift float64), each [L, K, n]; slots past a topic's last candidate
+        hold -1 / 0 / 0 / 0.0 / 0.0."""
+        n = int(n)
+        if not 1 <= n <= capi.TOP_WORDS_MAX:
+            raise ValueError(f"n must be in [1, {capi.TOP_WORDS_MAX}]")
+        lam = capi.check_lambdas(lambdas)
+        shape = (lam.size, self.K, n)
+        ids = np.zeros(shape, dtype=np.int32)
+        cnt = np.zeros(shape, dtype=np.int32)
+        tot = np.zeros(shape, dtype=np.int64)
+        lp = np.zeros(shape, dtype=np.float64)
+        ll = np.zeros(shape, dtype=np.float64)
+        capi.check(self._L.lda_relevant_words(self._h, n, lam.size, lam.ctypes.data, ids.ctypes.data, cnt.ctypes.data,
+                                              tot.ctypes.data, lp.ctypes.data, ll.ctypes.data), "lda_relevant_words")
+        return ids, cnt, tot, lp, ll
+
+    def salient_words(self, n: int):
+        """lda_salient_words: the n words of largest saliency (Chuang et al.
+        2012), equal values by ascending word id, selected on the device.
+        Returns (word_ids[n] int32, totals[n] int64, saliency[n],
+        distinctiveness[n] float64); -1 / 0 / 0.0 / 0.0 past the last word
+        with a token."""
+        n = int(n)
+        if not 1 <= n <= capi.SALIENT_WORDS_MAX:
+            raise ValueError(f"n must be in [1, {capi.SALIENT_WORDS_MAX}]")
+        ids = np.zeros(n, dtype=np.int32)
+        tot = np.zeros(n, dtype=np.int64)
+        sal = np.zeros(n, dtype=np.float64)
+        dist = np.zeros(n, dtype=np.float64)
+        capi.check(self._L.lda_salient_words(self._h, n, ids.ctypes.data, tot.ctypes.data, sal.ctypes.data,
+                                             dist.ctypes.data), "lda_salient_words")
+        return ids, tot, sal, dist
+
+    def word_rows(self, word_ids):
+        """lda_word_rows: (rows[M, K] int32, totals[M] int64) of the listed
+        words (any order, duplicates allowed), gathered on the device."""
+        ids = np.ascontiguousarray(word_ids, dtype=np.int32).reshape(-1)
+        if ids.size and (ids.min() < 0 or ids.max() >= self.V):
+            raise ValueError(f"word ids must be in [0, {self.V})")
+        rows = np.zeros((ids.size, self.K), dtype=np.int32)
+        tot = np.zeros(ids.size, dtype=np.int64)
+        capi.check(self._L.lda_word_rows(self._h, ids.size, ids.ctypes.data if ids.size else None,
+                                         rows.ctypes.data if ids.size else None,
+                                         tot.ctypes.data if ids.size else None), "lda_word_rows")
+        return rows, tot
+
     def doc_top_topics(self, m: int, docs=None, doc_begin: int = 0, num_docs: int | None = None):
         """lda_doc_top_topics: the m topics of each listed document with the
         largest weight (alpha_k + n_dk) / (n_d + alphaSum), equal weights by

@@ -92,6 +92,13 @@ TM_SIGNATURES = {
     "ldatm_print_top_words": (_i32, [_vp, C.c_char_p, _i32, _i32]),
     "ldatm_top_words_text": (_i32, [_vp, _i32, _i32, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "ldatm_topic_top_docs": (_i32, [_vp, _i32, C.c_double, _i32, _vp, _vp, _vp]),
+    "ldatm_relevant_words": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ldatm_salient_words": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp]),
+    "ldatm_word_rows": (_i32, [_vp, C.c_int64, _vp, _vp, _vp]),
+    "ldatm_print_relevant_words": (_i32, [_vp, C.c_char_p, _i32, C.c_double]),
+    "ldatm_relevant_words_text": (_i32, [_vp, _i32, C.c_double, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ldatm_relevant_words_format": (_i32, [_i32, _i32, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp,
+                                           C.c_size_t, C.POINTER(C.c_size_t)]),
     "ldatm_print_topic_documents": (_i32, [_vp, C.c_char_p, _i32, C.c_double, _i32]),
     "ldatm_topic_documents_text": (_i32, [_vp, _i32, C.c_double, _i32, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "ldatm_topic_documents_format": (_i32, [_i32, _i32, C.c_double, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_size_t,
@@ -223,6 +230,87 @@ def topic_phrases_bound(shard_counts, totals):
     _check(load_tm().ldatm_topic_phrases_bound(K, tot.shape[1], G, sc.ctypes.data, tot.ctypes.data,
                                                bound.ctypes.data, proven.ctypes.data), "ldatm_topic_phrases_bound")
     return bound, proven
+
+
+def format_relevant_words(word_ids, counts, totals, logprob, loglift, lambda_: float = 0.6, names=None) -> str:
+    """ldatm_relevant_words_format (host only, no device): printRelevantWords'
+    text from one lambda's [K, n] arrays as relevantWords returns them;
+    names[w] is word w's text (None, or no entry: the id)."""
+    ids = np.ascontiguousarray(word_ids, np.int32)
+    cnt = np.ascontiguousarray(counts, np.int32)
+    tot = np.ascontiguousarray(totals, np.int64)
+    lp = np.ascontiguousarray(logprob, np.float64)
+    ll = np.ascontiguousarray(loglift, np.float64)
+    if ids.ndim != 2 or any(a.shape != ids.shape for a in (cnt, tot, lp, ll)):
+        raise ValueError("word_ids, counts, totals, logprob and loglift must be [K, n] arrays of one shape")
+    K, n = ids.shape
+    names = list(names or [])
+    arr = (C.c_char_p * max(len(names), 1))(*[None if s is None else str(s).encode() for s in names])
+    L = load_tm()
+    size = C.c_size_t()
+    args = (K, n, float(lambda_), ids.ctypes.data, cnt.ctypes.data, tot.ctypes.data, lp.ctypes.data, ll.ctypes.data,
+            C.cast(arr, C.c_void_p), len(names))
+    _check(L.ldatm_relevant_words_format(*args, None, 0, C.byref(size)), "ldatm_relevant_words_format")
+    buf = C.create_string_buffer(size.value + 1)
+    _check(L.ldatm_relevant_words_format(*args, buf, size.value + 1, C.byref(size)), "ldatm_relevant_words_format")
+    return buf.value.decode()
+
+
+def classical_mds(dist) -> tuple:
+    """Classical (Torgerson) scaling of a symmetric K x K distance matrix to
+    two axes: B = -1/2 J D^2 J with J = I - 11'/K, numpy.linalg.eigh, the two
+    largest eigenvalues' vectors times sqrt(max(eigenvalue, 0)).  Each axis's
+    sign makes its entry of largest magnitude (the lowest index on a tie)
+    positive.  K = 1: both axes 0; K = 2: the y axis 0.  Returns (x[K], y[K])."""
+    D = np.asarray(dist, np.float64)
+    K = D.shape[0]
+    if D.ndim != 2 or D.shape[1] != K or K < 1:
+        raise ValueError("dist must be a square matrix")
+    x, y = np.zeros(K), np.zeros(K)
+    if K == 1:
+        return x, y
+    J = np.eye(K) - np.full((K, K), 1.0 / K)
+    w, v = np.linalg.eigh(-0.5 * (J @ (D * D) @ J))
+    axes = []
+    for j in (K - 1, K - 2)[:2 if K > 2 else 1]:
+        a = v[:, j] * np.sqrt(max(w[j], 0.0))
+        if a[int(np.argmax(np.abs(a)))] < 0:
+            a = -a
+        axes.append(a + 0.0)
+    x = axes[0]
+    if len(axes) > 1:
+        y = axes[1]
+    return x, y
+
+
+def vis_lambdas(step: float) -> np.ndarray:
+    """prepareVis' slider values 0, step, 2 step, ..., closed by 1.0: i * step
+    for i = 0 .. floor(1 / step + 1e-9), values above 1 taken as 1, and 1.0
+    appended when the last value is below it."""
+    step = float(step)
+    if not (np.isfinite(step) and 0.0 < step <= 1.0):
+        raise ValueError("lambdaStep must be in (0, 1]")
+    lam = [min(1.0, i * step) for i in range(int(np.floor(1.0 / step + 1e-9)) + 1)]
+    if lam[-1] < 1.0:
+        lam.append(1.0)
+    return np.array(lam, np.float64)
+
+
+class TopicRelevance:
+    """relevantWords' result: lambdas[L]; wordIds, counts (nw[w, k]) int32,
+    totals (tw[w]) int64, logprob, loglift float64, each [L, K, n], -1 / 0 / 0
+    / 0.0 / 0.0 past a topic's last candidate.  relevance(l): plane l's
+    [K, n] relevance, logprob - (1 - lambda) (logprob - loglift), NaN in an
+    empty slot."""
+
+    def __init__(self, lambdas, wordIds, counts, totals, logprob, loglift):
+        self.lambdas, self.wordIds, self.counts, self.totals = lambdas, wordIds, counts, totals
+        self.logprob, self.loglift = logprob, loglift
+
+    def relevance(self, l: int = 0) -> np.ndarray:
+        lp, ll = self.logprob[l], self.loglift[l]
+        r = lp - (1.0 - float(self.lambdas[l])) * (lp - ll)
+        return np.where(self.wordIds[l] >= 0, r, np.nan)
 
 
 class TopicPhrases:
@@ -572,6 +660,147 @@ class ParallelTopicModel:
         docs, w, _, _ = self.topicDocuments(n, smoothing, minTokens)
         return [[(int(d), float(x)) for d, x in zip(docs[k], w[k]) if d >= 0] for k in range(self.numTopics)]
 
+    # ------------------------------- relevance, saliency, LDAvis
+    def relevantWords(self, n: int, lambdas=0.6) -> TopicRelevance:
+        """ldatm_relevant_words: for each lambda (a scalar or up to
+        RELEVANCE_LAMBDAS_MAX values in [0, 1]) and topic the n words with
+        nw[w, k] > 0 of largest relevance lambda logprob + (1 - lambda) loglift,
+        equal keys by ascending word id, selected on the device."""
+        n = int(n)
+        if not 1 <= n <= capi.TOP_WORDS_MAX:
+            raise ValueError(f"n must be in [1, {capi.TOP_WORDS_MAX}]")
+        lam = capi.check_lambdas(lambdas)
+        shape = (lam.size, self.numTopics, n)
+        ids, cnt = np.zeros(shape, np.int32), np.zeros(shape, np.int32)
+        tot = np.zeros(shape, np.int64)
+        lp, ll = np.zeros(shape, np.float64), np.zeros(shape, np.float64)
+        _check(self._L.ldatm_relevant_words(self._h, n, lam.size, lam.ctypes.data, ids.ctypes.data, cnt.ctypes.data,
+                                            tot.ctypes.data, lp.ctypes.data, ll.ctypes.data), "relevantWords")
+        return TopicRelevance(lam, ids, cnt, tot, lp, ll)
+
+    def _word(self, w: int):
+        return int(w) if self.alphabet is None else self.alphabet.lookupObject(int(w))
+
+    def getRelevantWords(self, n: int = 10, lambda_: float = 0.6) -> list:
+        """Per topic a list of (word, relevance), at most n long, most relevant
+        first: the alphabet's entry, or the word id without an alphabet."""
+        if np.ndim(lambda_) != 0:
+            raise ValueError("lambda_ must be one value")
+        r = self.relevantWords(n, lambda_)
+        rel = r.relevance(0)
+        return [[(self._word(w), float(x)) for w, x in zip(r.wordIds[0, k], rel[k]) if w >= 0]
+                for k in range(self.numTopics)]
+
+    def salientWords(self, n: int = 30):
+        """ldatm_salient_words: (word_ids[n] int32, totals[n] int64,
+        saliency[n], distinctiveness[n] float64) of the n most salient words
+        (Chuang et al. 2012), equal values by ascending id; -1 / 0 / 0.0 / 0.0
+        past the last word with a token."""
+        n = int(n)
+        if not 1 <= n <= capi.SALIENT_WORDS_MAX:
+            raise ValueError(f"n must be in [1, {capi.SALIENT_WORDS_MAX}]")
+        ids, tot = np.zeros(n, np.int32), np.zeros(n, np.int64)
+        sal, dist = np.zeros(n, np.float64), np.zeros(n, np.float64)
+        _check(self._L.ldatm_salient_words(self._h, n, ids.ctypes.data, tot.ctypes.data, sal.ctypes.data,
+                                           dist.ctypes.data), "salientWords")
+        return ids, tot, sal, dist
+
+    def getSalientWords(self, n: int = 30) -> list:
+        """[(word, saliency), ...], at most n long, most salient first."""
+        ids, _, sal, _ = self.salientWords(n)
+        return [(self._word(w), float(x)) for w, x in zip(ids, sal) if w >= 0]
+
+    def wordRows(self, ids):
+        """ldatm_word_rows: (rows[M, K] int32, totals[M] int64) of the listed
+        words (any order, duplicates allowed), gathered on the device."""
+        w = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        if w.size and w.min() < 0:
+            raise ValueError("word ids must not be negative")
+        if w.size and self.alphabet is not None and w.max() >= self.alphabet.size():
+            raise ValueError(f"word ids must be in [0, {self.alphabet.size()})")
+        rows, tot = np.zeros((w.size, self.numTopics), np.int32), np.zeros(w.size, np.int64)
+        if w.size:
+            _check(self._L.ldatm_word_rows(self._h, w.size, w.ctypes.data, rows.ctypes.data, tot.ctypes.data),
+                   "wordRows")
+        return rows, tot
+
+    def prepareVis(self, R: int = 30, lambdaStep: float = 0.01) -> dict:
+        """The data of an LDAvis view as a dict in LDAvis's JSON layout
+        (createJSON's keys: mdsDat, tinfo, token.table, R, lambda.step,
+        plot.opts, topic.order), built from the device readouts: the R salient
+        terms, per topic the union of its R most relevant terms under each
+        lambda = 0, lambdaStep, ..., 1, the topics' token shares and a classical
+        MDS of their Jensen-Shannon distances.  Topics are shown by nwsum
+        descending (equal sums by ascending id); Freq of a topic's term is the
+        exact count nw[w, k], Total the word's total.  Only the lists leave the
+        device, never the V x K table."""
+        R = int(R)
+        if not 1 <= R <= capi.TOP_WORDS_MAX:
+            raise ValueError(f"R must be in [1, {capi.TOP_WORDS_MAX}]")
+        lam = vis_lambdas(lambdaStep)
+        K = self.numTopics
+        nwsum = np.zeros(K, np.int32)
+        _check(self._L.ldatm_get_counts(self._h, None, nwsum.ctypes.data), "ldatm_get_counts")
+        N = int(nwsum.astype(np.int64).sum())
+        order = sorted(range(K), key=lambda k: (-int(nwsum[k]), k))
+        rank = {k: i + 1 for i, k in enumerate(order)}
+        x, y = classical_mds(self.topicDistances(None, "jensen_shannon"))
+        sal_ids, sal_tot, _, _ = self.salientWords(R)
+        terms = [[] for _ in range(K)]       # per topic (word, count, total, logprob, loglift), first seen
+        seen = [set() for _ in range(K)]
+        for l0 in range(0, lam.size, capi.RELEVANCE_LAMBDAS_MAX):
+            r = self.relevantWords(R, lam[l0:l0 + capi.RELEVANCE_LAMBDAS_MAX])
+            for l in range(r.lambdas.size):
+                for k in range(K):
+                    for i in range(R):
+                        w = int(r.wordIds[l, k, i])
+                        if w < 0:
+                            break
+                        if w not in seen[k]:
+                            seen[k].add(w)
+                            terms[k].append((w, int(r.counts[l, k, i]), int(r.totals[l, k, i]),
+                                             float(r.logprob[l, k, i]), float(r.loglift[l, k, i])))
+        name = lambda w: str(self._word(w))
+        tinfo = {"Term": [], "Category": [], "Freq": [], "Total": [], "logprob": [], "loglift": []}
+
+        def add(term, cat, freq, total, lp, ll):
+            for key, v in zip(tinfo, (term, cat, freq, total, lp, ll)):
+                tinfo[key].append(v)
+
+        for i, (w, t) in enumerate(zip(sal_ids, sal_tot)):
+            if w >= 0:
+                add(name(w), "Default", int(t), int(t), float(R - i), float(R - i))
+        for k in order:
+            for w, c, t, lp, ll in terms[k]:
+                add(name(w), "Topic%d" % rank[k], c, t, lp, ll)
+        words = sorted({int(w) for w in sal_ids if w >= 0} | {w for k in range(K) for w in seen[k]})
+        rows, tot = self.wordRows(words)
+        table = {"Term": [], "Topic": [], "Freq": []}
+        for j, w in enumerate(words):
+            for k in order:
+                if rows[j, k] >= 1:
+                    table["Term"].append(name(w))
+                    table["Topic"].append(rank[k])
+                    table["Freq"].append(float(rows[j, k]) / float(tot[j]))
+        return {
+            "mdsDat": {"x": [float(x[k]) for k in order], "y": [float(y[k]) for k in order],
+                       "topics": list(range(1, K + 1)), "cluster": [1] * K,
+                       "Freq": [100.0 * float(nwsum[k]) / float(N) if N else 0.0 for k in order]},
+            "tinfo": tinfo,
+            "token.table": table,
+            "R": R,
+            "lambda.step": float(lambdaStep),
+            "plot.opts": {"xlab": "PC1", "ylab": "PC2"},
+            "topic.order": [k + 1 for k in order],
+        }
+
+    def saveVis(self, path, R: int = 30, lambdaStep: float = 0.01):
+        """prepareVis(R, lambdaStep) written to `path` with json.dump."""
+        import json
+        vis = self.prepareVis(R, lambdaStep)
+        with open(path, "w") as f:
+            json.dump(vis, f)
+
     # ------------------------------- topic phrases (DESIGN 9j)
     def topicPhrases(self, n: int, minLength: int = 2, maxLength: int = 32, minCount: int = 1):
         """ldatm_topic_phrases: per topic the n most frequent same-topic token
@@ -823,6 +1052,25 @@ class ParallelTopicModel:
     def printTopicDocuments(self, path, max: int = 100, smoothing: float = 10.0, minTokens: int = 1):
         _check(self._L.ldatm_print_topic_documents(self._h, os.fsencode(path), int(max), float(smoothing),
                                                    int(minTokens)), "printTopicDocuments")
+
+    def relevantWordsText(self, n: int = 10, lambda_: float = 0.6) -> str:
+        """printRelevantWords' text: "#topic rank word count total relevance
+        logprob loglift", then one such line per topic and rank."""
+        n, lam = self._relevance_args(n, lambda_)
+        return self._text(self._L.ldatm_relevant_words_text, n, lam)
+
+    def printRelevantWords(self, path, n: int = 10, lambda_: float = 0.6):
+        n, lam = self._relevance_args(n, lambda_)
+        _check(self._L.ldatm_print_relevant_words(self._h, os.fsencode(path), n, lam), "printRelevantWords")
+
+    @staticmethod
+    def _relevance_args(n, lambda_):
+        n = int(n)
+        if not 1 <= n <= capi.TOP_WORDS_MAX:
+            raise ValueError(f"n must be in [1, {capi.TOP_WORDS_MAX}]")
+        if np.ndim(lambda_) != 0:
+            raise ValueError("lambda_ must be one value")
+        return n, float(capi.check_lambdas(lambda_)[0])
 
     def topicPhrasesText(self, n: int = 10, minLength: int = 2, maxLength: int = 32, minCount: int = 1) -> str:
         """printTopicPhrases' text: "#topic rank count phrase", then per topic
