@@ -597,6 +597,49 @@ lda_status lda_topic_top_docs(lda_ctx* ctx, int32_t n, double smoothing, int32_t
  * documents instead of 2^23 / Kp (0 = the default). */
 void lda_debug_topic_docs_chunk_docs(int64_t docs);
 
+/* lda_topic_cooccurrence: which topics are used together in the same
+ * documents of THIS shard, counted on the device from the shard's current z
+ * (DESIGN.md §9l).  n_dk is document d's count of topic k, L_d its length.
+ *   A document is USED when L_d >= min_tokens (min_tokens >= 1).
+ *   Topic k is PRESENT in d when n_dk >= min_count and
+ *       (double) n_dk >= min_prop * (double) L_d
+ *   (min_count >= 1, 0 <= min_prop <= 1; one fp64 product and one compare).
+ * Over the used documents:
+ *   *docs_used  = their number
+ *   tokens[k]   = N_k  = sum over d of n_dk
+ *   present[k]  = C_k  = documents in which k is present
+ *   codocs[k*K + l]  = C_kl = documents in which k and l are both present;
+ *                      the diagonal is C_k
+ *   overlap[k*K + l] = M_kl = sum over d of min(n_dk, n_dl); the diagonal is N_k
+ *   product[k*K + l] = S_kl = sum over d of n_dk * n_dl; the diagonal is the
+ *                      sum of n_dk^2
+ * The three tables are full symmetric K x K, row-major; each is requested by
+ * a non-NULL pointer, and only the requested ones are allocated and
+ * accumulated.  overlap and product run over every nonzero topic of a used
+ * document: the two presence thresholds apply to present and codocs only.
+ * One wave per document; 64-bit integer adds only, so the result is a
+ * function of z and does not depend on the grid or the order of arrival.  Up
+ * to K = LDA_TOPIC_COOC_LDS_TOPICS a block accumulates the triangles in LDS
+ * and adds its nonzero cells once; above, every pair is a global atomic.
+ * Errors, checked on the host in this order before any device work:
+ * LDA_ERR_INVALID_ARG for a NULL ctx, a NULL docs_used / tokens / present,
+ * min_tokens < 1, min_count < 1, min_prop outside [0, 1] or NaN;
+ * LDA_ERR_STATE with a pending delta (call lda_apply first);
+ * LDA_ERR_UNSUPPORTED when product is requested and N * L_max >= 2^63 (N the
+ * shard's tokens, L_max of lda_max_doc_length: the bound of a product cell).
+ * D = 0 succeeds with zeros.  Changes no state of the context.
+ * Device scratch is grow-only and kept by the context: 8 (1 + 2 K) bytes and
+ * 8 K K bytes per requested table (128 MiB each at K = 4096), all of which is
+ * copied to the host.  Waits once for the context's stream. */
+#define LDA_TOPIC_COOC_LDS_TOPICS 64
+lda_status lda_topic_cooccurrence(lda_ctx* ctx, int64_t min_tokens, int32_t min_count, double min_prop,
+                                  int64_t* docs_used, int64_t* tokens /*[K]*/, int64_t* present /*[K]*/,
+                                  int64_t* codocs /*[K*K] or NULL*/, int64_t* overlap /*[K*K] or NULL*/,
+                                  int64_t* product /*[K*K] or NULL*/);
+/* Test and measurement hook: on != 0 makes lda_topic_cooccurrence use global
+ * atomics at every K (0 = the default, LDS up to LDA_TOPIC_COOC_LDS_TOPICS). */
+void lda_debug_topic_cooccurrence_global(int32_t on);
+
 /* Relevance-ranked topic words, salient terms and word rows: what an LDAvis
  * view of a trained model shows, selected on the device from the global counts
  * this shard holds (the int32 nw rows, V x Kp, and nwsum), without the V x K
@@ -1055,8 +1098,10 @@ void lda_debug_fail_host_alloc(int32_t nth);
  * hook lda_debug_topic_docs_chunk_docs), then lda_topic_phrases,
  * lda_phrase_counts and lda_phrase_lookup (with their test hook
  * lda_debug_phrase_table_slots), then lda_relevant_words, lda_salient_words
- * and lda_word_rows (with their test hook lda_debug_relevance_slab_rows) came
- * later and only add symbols, so the version stays 8. */
+ * and lda_word_rows (with their test hook lda_debug_relevance_slab_rows), then
+ * lda_topic_cooccurrence (with its test hook
+ * lda_debug_topic_cooccurrence_global) came later and only add symbols, so the
+ * version stays 8. */
 #define LDA_ABI_VERSION 8
 const char* lda_version(void);
 int32_t lda_abi_version(void);

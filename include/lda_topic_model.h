@@ -408,6 +408,79 @@ lda_status ldatm_topic_documents_format(int32_t K, int32_t n, double smoothing, 
                                         const int32_t* counts, const int32_t* lengths, const char* const* names,
                                         int64_t num_names, char* buf, size_t cap, size_t* len);
 
+/* Topic co-occurrence in documents: which topics are used together
+ * (lda_topic_cooccurrence of lda_mi355x.h; the question of
+ * stm::topicCorr and jsLDA's topic correlations).
+ * ldatm_topic_cooccurrence: lda_topic_cooccurrence's outputs summed over the
+ * model's shards -- integer sums, so the result does not depend on the number
+ * of shards.  A document is used with at least min_tokens tokens; topic k is
+ * present in it with n_dk >= min_count and (double) n_dk >= min_prop *
+ * (double) L_d.  *docs_used, tokens[K] (N_k), present[K] (C_k) are required;
+ * codocs (C_kl), overlap (M_kl = sum of min(n_dk, n_dl)) and product (S_kl =
+ * sum of n_dk n_dl), full symmetric K x K, are each counted only when the
+ * pointer is not NULL.
+ * ldatm_topic_correlation_finish (host only, no model and no device): a K x K
+ * matrix of doubles from those integers, D' = docs_used:
+ *   LDATM_CORR_PMI      codocs   log(D' C_kl / (C_k C_l))
+ *   LDATM_CORR_NPMI     codocs   pmi / -log(C_kl / D')
+ *   LDATM_CORR_JACCARD  codocs   C_kl / (C_k + C_l - C_kl)
+ *   LDATM_CORR_OVERLAP  overlap  M_kl / (N_k + N_l - M_kl)
+ *   LDATM_CORR_COSINE   product  S_kl / (sqrt(S_kk) sqrt(S_ll))
+ *   LDATM_CORR_PEARSON  product  (D' S_kl - N_k N_l) /
+ *                                sqrt((D' S_kk - N_k^2) (D' S_ll - N_l^2))
+ * pmi is -inf when C_kl = 0 and NaN when C_k or C_l is 0; npmi is -1 when
+ * C_kl = 0, 1 when C_kl = D', NaN when C_k or C_l is 0; the others are NaN
+ * when a denominator term is 0.  Every integer becomes a double once, then one
+ * rounding per operation; Pearson's three terms are formed exactly in 128-bit
+ * integers before that one conversion, so the measure has no cancellation
+ * error.  table_kind says which table `table` is (LDATM_COOC_*): one that is
+ * not the measure's, or an unknown measure, is LDA_ERR_INVALID_ARG with a
+ * message.
+ * ldatm_topic_correlations: counts only the table the measure needs, then
+ * finishes; out[K*K].
+ * ldatm_topic_partners: per topic its n strongest other topics by that
+ * matrix: larger value first, equal values by smaller id, non-finite values
+ * left out; ids / values [K*n], -1 / NaN past the last partner (n > K - 1
+ * always has such slots).  The selection is on the host from the K x K matrix
+ * (ldatm_topic_partners_select, host only, does it from a given matrix).
+ * ldatm_topic_correlations_text / ldatm_print_topic_correlations: the partners
+ * as text, "#topic partner value\n", then "<topic> <partner> <value>\n" per
+ * topic and rank (Java Double.toString, as ldatm_format_double style 0);
+ * empty slots print nothing.  ldatm_topic_correlations_format: that text from
+ * the caller's K x n arrays (host only).
+ * Errors, checked before any device work (a model without a GPU names its bad
+ * argument): LDA_ERR_INVALID_ARG for a NULL model, an unknown measure,
+ * min_tokens < 1, min_count < 1, min_prop outside [0, 1] or NaN, n < 1, a NULL
+ * output. */
+#define LDATM_CORR_PMI 0
+#define LDATM_CORR_NPMI 1
+#define LDATM_CORR_JACCARD 2
+#define LDATM_CORR_OVERLAP 3
+#define LDATM_CORR_COSINE 4
+#define LDATM_CORR_PEARSON 5
+#define LDATM_COOC_CODOCS 0
+#define LDATM_COOC_OVERLAP 1
+#define LDATM_COOC_PRODUCT 2
+lda_status ldatm_topic_cooccurrence(ldatm* m, int64_t min_tokens, int32_t min_count, double min_prop,
+                                    int64_t* docs_used, int64_t* tokens /*[K]*/, int64_t* present /*[K]*/,
+                                    int64_t* codocs /*[K*K] or NULL*/, int64_t* overlap /*[K*K] or NULL*/,
+                                    int64_t* product /*[K*K] or NULL*/);
+lda_status ldatm_topic_correlation_finish(int32_t measure, int32_t K, int64_t docs_used, const int64_t* tokens,
+                                          const int64_t* present, int32_t table_kind, const int64_t* table,
+                                          double* out /*[K*K]*/);
+lda_status ldatm_topic_correlations(ldatm* m, int32_t measure, int64_t min_tokens, int32_t min_count,
+                                    double min_prop, double* out /*[K*K]*/);
+lda_status ldatm_topic_partners(ldatm* m, int32_t measure, int64_t min_tokens, int32_t min_count, double min_prop,
+                                int32_t n, int32_t* ids /*[K*n]*/, double* values /*[K*n]*/);
+lda_status ldatm_topic_partners_select(int32_t K, int32_t n, const double* matrix /*[K*K]*/, int32_t* ids /*[K*n]*/,
+                                       double* values /*[K*n]*/);
+lda_status ldatm_topic_correlations_text(ldatm* m, int32_t measure, int32_t n, int64_t min_tokens,
+                                         int32_t min_count, double min_prop, char* buf, size_t cap, size_t* len);
+lda_status ldatm_print_topic_correlations(ldatm* m, const char* path, int32_t measure, int32_t n,
+                                          int64_t min_tokens, int32_t min_count, double min_prop);
+lda_status ldatm_topic_correlations_format(int32_t K, int32_t n, const int32_t* ids, const double* values,
+                                           char* buf, size_t cap, size_t* len);
+
 /* Relevance-ranked topic words, salient terms and word rows: what an LDAvis
  * view shows (lda_relevant_words, lda_salient_words and lda_word_rows of
  * lda_mi355x.h, which states the definitions).  They run on shard 0

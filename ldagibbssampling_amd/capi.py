@@ -36,6 +36,35 @@ TOP_WORDS_MAX = 64
 TOP_TOPICS_MAX = 64
 # LDA_TOPIC_DOCS_MAX of lda_mi355x.h
 TOPIC_DOCS_MAX = 128
+# LDA_TOPIC_COOC_LDS_TOPICS of lda_mi355x.h: lda_topic_cooccurrence accumulates in
+# LDS up to this K, with global atomics above
+TOPIC_COOC_LDS_TOPICS = 64
+# lda_topic_cooccurrence's optional K x K tables, in the order of its arguments
+TOPIC_COOC_STATS = ("codocs", "overlap", "product")
+
+
+def topic_cooc_stats(stats) -> tuple:
+    """The requested tables of lda_topic_cooccurrence as a tuple of names, in
+    the call's order; a single name is accepted."""
+    if isinstance(stats, str):
+        stats = (stats,)
+    stats = tuple(stats)
+    for s in stats:
+        if s not in TOPIC_COOC_STATS:
+            raise ValueError(f"unknown statistic {s!r}: one of {TOPIC_COOC_STATS}")
+    return tuple(s for s in TOPIC_COOC_STATS if s in stats)
+
+
+def topic_cooc_thresholds(min_tokens, min_count, min_prop) -> tuple:
+    """lda_topic_cooccurrence's thresholds, checked as the library checks them."""
+    min_tokens, min_count, min_prop = int(min_tokens), int(min_count), float(min_prop)
+    if min_tokens < 1:
+        raise ValueError("min_tokens must be at least 1")
+    if min_count < 1:
+        raise ValueError("min_count must be at least 1")
+    if not 0.0 <= min_prop <= 1.0:
+        raise ValueError("min_prop must be in [0, 1]")
+    return min_tokens, min_count, min_prop
 # LDA_RELEVANCE_LAMBDAS_MAX / LDA_SALIENT_WORDS_MAX of lda_mi355x.h
 RELEVANCE_LAMBDAS_MAX = 128
 SALIENT_WORDS_MAX = 256
@@ -212,6 +241,8 @@ SIGNATURES = {
     "lda_debug_cooc_chunk_tokens": (None, [C.c_int64]),
     "lda_topic_top_docs": (C.c_int32, [_vp, C.c_int32, C.c_double, C.c_int32, _vp, _vp, _vp]),
     "lda_debug_topic_docs_chunk_docs": (None, [C.c_int64]),
+    "lda_topic_cooccurrence": (C.c_int32, [_vp, C.c_int64, C.c_int32, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lda_debug_topic_cooccurrence_global": (None, [C.c_int32]),
     "lda_relevant_words": (C.c_int32, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lda_salient_words": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, _vp]),
     "lda_word_rows": (C.c_int32, [_vp, C.c_int64, _vp, _vp, _vp]),

@@ -250,6 +250,8 @@ constexpr int64_t TOPIC_DOCS_WAVES = 1024;
 static_assert(LDA_TOPIC_DOCS_MAX == lda::TOPIC_DOCS_MAX, "the header states the kernels' limit");
 static_assert(TOPIC_DOCS_WAVES <= lda::TOPIC_DOCS_MAX_SLABS, "the merge holds every slab's head");
 int64_t g_topic_docs_chunk = 0;   // lda_debug_topic_docs_chunk_docs (0: TOPIC_DOCS_CELLS / Kp)
+static_assert(LDA_TOPIC_COOC_LDS_TOPICS == lda::TOPIC_COOC_LDS_TOPICS, "the header states the kernel's boundary");
+int32_t g_topic_cooc_global = 0;  // lda_debug_topic_cooccurrence_global (1: global atomics at every K)
 // lda_topic_phrases / lda_phrase_counts: the table has the smallest power of
 // two of slots >= 2 * (N / min_len), between PHRASE_MIN_SLOTS and
 // PHRASE_MAX_SLOTS (12 bytes a slot: 3 GiB, and 4 more for the selection's
@@ -414,6 +416,10 @@ struct lda_ctx {
   unsigned long long* td_bits = nullptr;
   int64_t *td_ids = nullptr, *td_out_ids = nullptr;
   size_t td_cap[6] = {};
+  // lda_topic_cooccurrence: grow-only scratch -- docs_used, tokens [K],
+  // present [K], then the requested K x K tables
+  unsigned long long* tc_buf = nullptr;
+  size_t tc_cap = 0;
   // lda_relevant_words / lda_salient_words / lda_word_rows: grow-only scratch
   // -- N [1], the word totals and their logs [V], the distinctiveness [V], the
   // slab lists (keys, ids), the results of a pass (int32, int64, fp64), a
@@ -587,6 +593,7 @@ struct lda_ctx {
                     (void*)dg_ids, (void*)dg_table, (void*)dg_out, (void*)dg_shares,
                     (void*)cc_moff, (void*)cc_mem, (void*)cc_words, (void*)cc_out, (void*)cc_off,
                     (void*)td_rows, (void*)td_cnts, (void*)td_out, (void*)td_bits, (void*)td_ids, (void*)td_out_ids,
+                    (void*)tc_buf,
                     (void*)rv_ntot, (void*)rv_tw, (void*)rv_out64, (void*)rv_logtp, (void*)rv_dist, (void*)rv_outd,
                     (void*)rv_keys, (void*)rv_ids, (void*)rv_out32, (void*)rv_list, (void*)rv_rows,
                     (void*)ph_keys, (void*)ph_u64, (void*)ph_sel_key, (void*)ph_cnts, (void*)ph_cand, (void*)ph_u32,
@@ -3362,6 +3369,76 @@ lda_status lda_topic_word_stats(lda_ctx* c, int32_t n, const int32_t* word_ids, 
   HIP_TRY(hipMemcpyAsync(share_sums, a.share_sums, sizeof(double) * cells, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(sumsq, a.sumsq, sizeof(uint64_t) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return LDA_OK;
+  });
+}
+
+void lda_debug_topic_cooccurrence_global(int32_t on) { g_topic_cooc_global = on != 0; }
+
+lda_status lda_topic_cooccurrence(lda_ctx* c, int64_t min_tokens, int32_t min_count, double min_prop,
+                                  int64_t* docs_used, int64_t* tokens, int64_t* present, int64_t* codocs,
+                                  int64_t* overlap, int64_t* product) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (!docs_used || !tokens || !present)
+    return fail(LDA_ERR_INVALID_ARG, "null output (docs_used, tokens and present are required)");
+  if (min_tokens < 1) return fail(LDA_ERR_INVALID_ARG, "min_tokens must be at least 1");
+  if (min_count < 1) return fail(LDA_ERR_INVALID_ARG, "min_count must be at least 1");
+  if (!(min_prop >= 0.0 && min_prop <= 1.0)) return fail(LDA_ERR_INVALID_ARG, "min_prop must be in [0, 1]");
+  if (c->pending) return fail(LDA_ERR_STATE, "topic co-occurrence with a pending delta: call lda_apply first");
+  const size_t K = (size_t)c->K, cells = K * K, head = 1 + 2 * K;
+  if (product) {
+    int32_t lmax = 0;
+    lda_max_doc_length(c, &lmax);
+    // a product cell is at most sum_d L_d^2 <= N L_max
+    if ((unsigned __int128)c->N * (unsigned __int128)lmax >= ((unsigned __int128)1 << 63))
+      return fail(LDA_ERR_UNSUPPORTED, "topic co-occurrence: product with tokens x longest document >= 2^63");
+  }
+  int64_t* outs[3] = {codocs, overlap, product};
+  size_t ntab = 0;
+  for (int64_t* o : outs) ntab += o != nullptr;
+  if (c->D == 0) {
+    *docs_used = 0;
+    std::fill(tokens, tokens + K, (int64_t)0);
+    std::fill(present, present + K, (int64_t)0);
+    for (int64_t* o : outs)
+      if (o) std::fill(o, o + cells, (int64_t)0);
+    return LDA_OK;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t total = head + ntab * cells;
+  HIP_TRY(grow_bytes(reinterpret_cast<void**>(&c->tc_buf), &c->tc_cap, total * sizeof(unsigned long long)));
+  HIP_TRY(hipMemsetAsync(c->tc_buf, 0, total * sizeof(unsigned long long), c->stream));
+  lda::TopicCoocArgs a{};
+  a.z = c->z;
+  a.doc_off = c->doc_off;
+  a.D = c->D;
+  a.min_tokens = min_tokens;
+  a.min_prop = min_prop;
+  a.min_count = min_count;
+  a.K = c->K;
+  a.Kp = c->Kp;
+  a.head = c->tc_buf;
+  unsigned long long* next = c->tc_buf + head;
+  unsigned long long** tabs[3] = {&a.codocs, &a.overlap, &a.product};
+  for (int t = 0; t < 3; ++t)
+    if (outs[t]) {
+      *tabs[t] = next;
+      next += cells;
+    }
+  const int lds = c->K <= LDA_TOPIC_COOC_LDS_TOPICS && !g_topic_cooc_global;
+  const int blocks = (int)std::min<int64_t>((c->D + 3) / 4, (int64_t)c->cus * 8);
+  HIP_TRY(lda::launch_topic_cooc(a, blocks, lds, c->stream));
+  // the head lands in a host buffer of its own: three outputs, one copy
+  std::vector<int64_t> hd = host_vector<int64_t>(head);
+  HIP_TRY(hipMemcpyAsync(hd.data(), a.head, sizeof(int64_t) * head, hipMemcpyDeviceToHost, c->stream));
+  for (int t = 0; t < 3; ++t)
+    if (outs[t])
+      HIP_TRY(hipMemcpyAsync(outs[t], *tabs[t], sizeof(int64_t) * cells, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  *docs_used = hd[0];
+  std::copy(hd.begin() + 1, hd.begin() + 1 + (std::ptrdiff_t)K, tokens);
+  std::copy(hd.begin() + 1 + (std::ptrdiff_t)K, hd.end(), present);
   return LDA_OK;
   });
 }

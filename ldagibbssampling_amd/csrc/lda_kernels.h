@@ -674,5 +674,31 @@ struct WordRowsArgs {
   long long* totals;             // [M]
 };
 hipError_t launch_word_rows(const WordRowsArgs& a, hipStream_t st);
+// lda_topic_cooccurrence: k_topic_cooc, one wave per document
+// of at least min_tokens tokens, builds the document's topic counts in its LDS
+// histogram, compacts the distinct topics into a 16-bit LDS list of m entries
+// and spreads the m (m + 1) / 2 pairs (i <= j) over its lanes.  Topic k is
+// present when n_dk >= min_count and (double) n_dk >= min_prop * (double) L_d.
+// head = docs_used, tokens[K], present[K]; each non-NULL table gets, at cell
+// (min(k, l), max(k, l)) of its K x K rows, 1 when both are present (codocs),
+// min(n_dk, n_dl) (overlap), n_dk * n_dl (product).  Only the upper triangle
+// is written: k_topic_cooc_mirror copies it below the diagonal.  Everything
+// must be zero before the launch.  With lds != 0 (K <= TOPIC_COOC_LDS_TOPICS)
+// a block keeps the head and the packed triangles of the requested tables in
+// LDS as 64-bit cells and adds its nonzero cells once at its end; otherwise
+// every add is a global 64-bit integer atomic.
+constexpr int TOPIC_COOC_LDS_TOPICS = 64;
+struct TopicCoocArgs {
+  const int32_t* z;
+  const int64_t* doc_off;
+  int64_t D, min_tokens;
+  double min_prop;
+  int32_t min_count, K, Kp;
+  unsigned long long* head;      // [1 + 2 K]
+  unsigned long long* codocs;    // [K * K] or NULL
+  unsigned long long* overlap;   // [K * K] or NULL
+  unsigned long long* product;   // [K * K] or NULL
+};
+hipError_t launch_topic_cooc(const TopicCoocArgs& a, int blocks, int lds, hipStream_t st);
 
 }  // namespace lda

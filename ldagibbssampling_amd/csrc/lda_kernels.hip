@@ -6211,4 +6211,169 @@ hipError_t launch_word_rows(const WordRowsArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// lda_topic_cooccurrence: one wave per used document (L_d >= min_tokens),
+// grid-capped as k_doc_diag.  LDS per wave: the histogram [Kp] (uint32) and
+// the list [Kp] (uint16) of the document's distinct topics, 24 KiB at
+// Kp = 4096; the four lists lie behind the four histograms.
+//   1. the histogram from z (LDS adds);
+//   2. the list, in O(tokens): every token sets bit 31 of its topic's cell,
+//      and the lane that finds the bit clear owns the topic; a ballot and a
+//      prefix count give the owners their slots, m grows by the ballot's count
+//      (a count stays below 2^31, lda_max_doc_length is an int32);
+//   3. lane e adds entry e's count to tokens and, if the topic is present, 1
+//      to present; lane 0 adds 1 to docs_used;
+//   4. the pairs (i <= j) of the list are the m rows of a triangle; row r
+//      (r + 1 entries) and row m - 1 - r (m - r entries) together are m + 1
+//      long, so p = r (m + 1) + q enumerates the pairs with ceil(m / 2) (m + 1)
+//      indices, of which an odd m's middle row wastes (m + 1) / 2.  Lane
+//      p mod 64 adds to cell (smaller topic, larger topic) of the requested
+//      tables; the diagonal (i == j) needs no case of its own;
+//   5. the histogram is cleared through the list.
+// LDS != 0: the adds go to the block's 64-bit LDS cells -- head [1 + 2 K], then
+// the packed triangle [K (K + 1) / 2] of every requested table, (k, l), k >= l,
+// at k (k + 1) / 2 + l -- and the block adds its nonzero cells to global memory
+// once.  Otherwise they are global atomics.  Integer adds only: the result is
+// a function of z, whatever the grid and the order.
+template <bool LDS>
+__global__ __launch_bounds__(256) void k_topic_cooc(const TopicCoocArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int32_t h[];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int K = a.K, T = K * (K + 1) / 2;
+  uint32_t* hist = reinterpret_cast<uint32_t*>(h) + wid * a.Kp;
+  uint16_t* list = reinterpret_cast<uint16_t*>(h + 4 * a.Kp) + wid * a.Kp;
+  unsigned long long* blk = reinterpret_cast<unsigned long long*>(h + 6 * a.Kp);
+  const int ntab = (a.codocs != nullptr) + (a.overlap != nullptr) + (a.product != nullptr);
+  const int blk_cells = 1 + 2 * K + ntab * T;
+  // where a table's triangle starts in blk (LDS only)
+  const int o_cod = 1 + 2 * K, o_ovl = o_cod + (a.codocs ? T : 0), o_prd = o_ovl + (a.overlap ? T : 0);
+  auto add = [&](unsigned long long* g, int o, size_t cell, unsigned long long v) {
+    if (LDS)
+      atomicAdd(&blk[o + cell], v);
+    else
+      atomicAdd(&g[cell], v);
+  };
+  for (int i = lane; i < a.Kp; i += 64) hist[i] = 0;
+  if (LDS)
+    for (int i = threadIdx.x; i < blk_cells; i += 256) blk[i] = 0;
+  __syncthreads();
+  const int32_t* __restrict__ z = a.z;
+  for (int64_t d = (int64_t)blockIdx.x * 4 + wid; d < a.D; d += (int64_t)gridDim.x * 4) {
+    const int64_t t0 = a.doc_off[d], t1 = a.doc_off[d + 1], L = t1 - t0;
+    if (L < a.min_tokens) continue;
+    for (int64_t i = t0 + lane; i < t1; i += 64) atomicAdd(&hist[z[i]], 1u);
+    wave_lds_fence();
+    int m = 0;
+    for (int64_t b = t0; b < t1; b += 64) {
+      const int64_t i = b + lane;
+      int k = 0;
+      bool own = false;
+      if (i < t1) {
+        k = z[i];
+        own = (atomicOr(&hist[k], 0x80000000u) >> 31) == 0;
+      }
+      const uint64_t owners = __ballot(own);
+      if (own) list[m + __popcll(owners & ((1ull << lane) - 1))] = (uint16_t)k;
+      m += __popcll(owners);
+    }
+    wave_lds_fence();
+    const double thr = a.min_prop * (double)L;
+    auto count = [&](int k) { return (int32_t)(hist[k] & 0x7FFFFFFFu); };
+    auto here = [&](int32_t c) { return c >= a.min_count && (double)c >= thr; };
+    if (lane == 0) add(a.head, 0, 0, 1ull);
+    for (int e = lane; e < m; e += 64) {
+      const int k = list[e];
+      const int32_t c = count(k);
+      add(a.head, 0, 1 + k, (unsigned long long)c);
+      if (here(c)) add(a.head, 0, 1 + K + k, 1ull);
+    }
+    if (ntab) {
+      const int w = m + 1, P = ((m + 1) >> 1) * w;
+      for (int p = lane; p < P; p += 64) {
+        const int r = p / w, q = p - r * w;
+        int i = q, j = r;
+        if (q > r) {
+          i = q - r - 1;
+          j = m - 1 - r;
+          if (j == r) continue;   // an odd m's middle row, already taken
+        }
+        const int ki = list[i], kj = list[j];
+        const int32_t ci = count(ki), cj = count(kj);
+        const int lo = min(ki, kj), hi = max(ki, kj);
+        const size_t cell = LDS ? (size_t)(hi * (hi + 1) / 2 + lo) : (size_t)lo * K + hi;
+        if (a.codocs && here(ci) && here(cj)) add(a.codocs, o_cod, cell, 1ull);
+        if (a.overlap) add(a.overlap, o_ovl, cell, (unsigned long long)min(ci, cj));
+        if (a.product) add(a.product, o_prd, cell, (unsigned long long)ci * (unsigned long long)cj);
+      }
+    }
+    wave_lds_fence();
+    for (int e = lane; e < m; e += 64) hist[list[e]] = 0;
+    wave_lds_fence();
+  }
+  if (!LDS) return;
+  __syncthreads();
+  for (int i = threadIdx.x; i < 1 + 2 * K; i += 256) {
+    const unsigned long long v = blk[i];
+    if (v) atomicAdd(&a.head[i], v);
+  }
+  for (int i = threadIdx.x; i < K * K; i += 256) {
+    const int lo = i / K, hi = i - lo * K;
+    if (hi < lo) continue;
+    const int t = hi * (hi + 1) / 2 + lo;
+    if (a.codocs) {
+      const unsigned long long v = blk[o_cod + t];
+      if (v) atomicAdd(&a.codocs[i], v);
+    }
+    if (a.overlap) {
+      const unsigned long long v = blk[o_ovl + t];
+      if (v) atomicAdd(&a.overlap[i], v);
+    }
+    if (a.product) {
+      const unsigned long long v = blk[o_prd + t];
+      if (v) atomicAdd(&a.product[i], v);
+    }
+  }
+}
+
+// lda_topic_cooccurrence: cell (k, l), l < k, takes cell (l, k)'s value
+__global__ __launch_bounds__(256) void k_topic_cooc_mirror(unsigned long long* __restrict__ t, int K) {
+  const int64_t cells = (int64_t)K * K;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < cells; i += (int64_t)gridDim.x * 256) {
+    const int64_t r = i / K, c = i - r * K;
+    if (c < r) t[i] = t[c * K + r];
+  }
+}
+
+hipError_t launch_topic_cooc(const TopicCoocArgs& a, int blocks, int lds, hipStream_t st) {
+  if (a.K < 1 || a.K > a.Kp || a.Kp > 4096 || (a.Kp & 63) != 0 || blocks < 1 || a.min_tokens < 1 || a.min_count < 1 ||
+      !a.head || (lds && a.K > TOPIC_COOC_LDS_TOPICS))
+    return hipErrorInvalidValue;
+  if (a.D <= 0) return hipSuccess;
+  // four histograms and four 16-bit lists: 96 KiB at Kp = 4096
+  size_t bytes = 4 * (size_t)a.Kp * (sizeof(uint32_t) + sizeof(uint16_t));
+  unsigned long long* tables[3] = {a.codocs, a.overlap, a.product};
+  int ntab = 0;
+  for (unsigned long long* t : tables) ntab += t != nullptr;
+  if (lds) bytes += (1 + 2 * (size_t)a.K + (size_t)ntab * (a.K * (a.K + 1) / 2)) * sizeof(unsigned long long);
+  const void* fn = lds ? reinterpret_cast<const void*>(&k_topic_cooc<true>)
+                       : reinterpret_cast<const void*>(&k_topic_cooc<false>);
+  if (bytes > 65536) {   // Kp > 2730: past the default dynamic LDS limit
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return e;
+  }
+  if (lds)
+    hipLaunchKernelGGL(k_topic_cooc<true>, dim3(blocks), dim3(256), bytes, st, a);
+  else
+    hipLaunchKernelGGL(k_topic_cooc<false>, dim3(blocks), dim3(256), bytes, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || ntab == 0 || a.K < 2) return e;
+  const int mirror_blocks = (int)std::min<int64_t>(((int64_t)a.K * a.K + 255) / 256, 2048);
+  for (unsigned long long* t : tables)
+    if (t) {
+      hipLaunchKernelGGL(k_topic_cooc_mirror, dim3(mirror_blocks), dim3(256), 0, st, t, a.K);
+      e = hipGetLastError();
+      if (e != hipSuccess) return e;
+    }
+  return hipSuccess;
+}
+
 }  // namespace lda

@@ -1336,6 +1336,201 @@ std::string ParallelTopicModel::topicPhrasesText(int32_t n, int32_t min_len, int
   });
 }
 
+// ---- topic co-occurrence -----------------------------------
+namespace {
+// lda_topic_cooccurrence's argument checks, before any shard is built
+void checkCooccurrence(int64_t min_tokens, int32_t min_count, double min_prop) {
+  if (min_tokens < 1) raise(LDA_ERR_INVALID_ARG, "min_tokens must be at least 1");
+  if (min_count < 1) raise(LDA_ERR_INVALID_ARG, "min_count must be at least 1");
+  if (!(min_prop >= 0.0 && min_prop <= 1.0)) raise(LDA_ERR_INVALID_ARG, "min_prop must be in [0, 1]");
+}
+void checkMeasure(int32_t measure) {
+  if (correlationTable(measure) < 0) raise(LDA_ERR_INVALID_ARG, "unknown measure (LDATM_CORR_*)");
+}
+}  // namespace
+
+int32_t correlationTable(int32_t measure) {
+  switch (measure) {
+    case LDATM_CORR_PMI:
+    case LDATM_CORR_NPMI:
+    case LDATM_CORR_JACCARD:
+      return LDATM_COOC_CODOCS;
+    case LDATM_CORR_OVERLAP:
+      return LDATM_COOC_OVERLAP;
+    case LDATM_CORR_COSINE:
+    case LDATM_CORR_PEARSON:
+      return LDATM_COOC_PRODUCT;
+    default:
+      return -1;
+  }
+}
+
+void topicCorrelationFinish(int32_t measure, int32_t K, int64_t docs_used, const int64_t* tokens,
+                            const int64_t* present, int32_t table_kind, const int64_t* table, double* out) {
+  checkMeasure(measure);
+  if (K < 1) raise(LDA_ERR_INVALID_ARG, "K must be at least 1");
+  if (docs_used < 0) raise(LDA_ERR_INVALID_ARG, "docs_used must not be negative");
+  if (!tokens || !present || !table) raise(LDA_ERR_INVALID_ARG, "null input (tokens, present, table)");
+  if (!out) raise(LDA_ERR_INVALID_ARG, "null output");
+  if (table_kind != correlationTable(measure))
+    raise(LDA_ERR_INVALID_ARG, "wrong table for the measure: pmi, npmi and jaccard take codocs, overlap takes "
+                               "overlap, cosine and pearson take product");
+  const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+  const double D = (double)docs_used;
+  const size_t Ks = (size_t)K;
+  for (size_t k = 0; k < Ks; ++k)
+    for (size_t l = 0; l < Ks; ++l) {
+      const int64_t t = table[k * Ks + l];
+      double v = nan;
+      switch (measure) {
+        case LDATM_CORR_PMI:
+        case LDATM_CORR_NPMI: {
+          const int64_t ck = present[k], cl = present[l];
+          if (ck == 0 || cl == 0) break;
+          const bool npmi = measure == LDATM_CORR_NPMI;
+          if (t == 0) {
+            v = npmi ? -1.0 : -inf;
+          } else if (npmi && t == docs_used) {
+            v = 1.0;
+          } else {
+            const double pmi = std::log(D * (double)t / ((double)ck * (double)cl));
+            v = npmi ? pmi / -std::log((double)t / D) : pmi;
+          }
+          break;
+        }
+        case LDATM_CORR_JACCARD: {
+          const int64_t u = present[k] + present[l] - t;
+          if (u != 0) v = (double)t / (double)u;
+          break;
+        }
+        case LDATM_CORR_OVERLAP: {
+          const int64_t u = tokens[k] + tokens[l] - t;
+          if (u != 0) v = (double)t / (double)u;
+          break;
+        }
+        case LDATM_CORR_COSINE: {
+          const int64_t skk = table[k * Ks + k], sll = table[l * Ks + l];
+          if (skk != 0 && sll != 0) v = (double)t / (std::sqrt((double)skk) * std::sqrt((double)sll));
+          break;
+        }
+        default: {   // LDATM_CORR_PEARSON: the three terms exactly, then one conversion each
+          const __int128 Dp = docs_used, nk = tokens[k], nl = tokens[l];
+          const __int128 cov = Dp * t - nk * nl;
+          const __int128 vk = Dp * table[k * Ks + k] - nk * nk, vl = Dp * table[l * Ks + l] - nl * nl;
+          if (vk != 0 && vl != 0) v = (double)cov / std::sqrt((double)vk * (double)vl);
+          break;
+        }
+      }
+      out[k * Ks + l] = v;
+    }
+}
+
+void topicPartnersSelect(int32_t K, int32_t n, const double* matrix, int32_t* ids, double* values) {
+  if (K < 1) raise(LDA_ERR_INVALID_ARG, "K must be at least 1");
+  if (n < 1) raise(LDA_ERR_INVALID_ARG, "n must be at least 1");
+  if (!matrix) raise(LDA_ERR_INVALID_ARG, "null matrix");
+  if (!ids || !values) raise(LDA_ERR_INVALID_ARG, "null output");
+  std::vector<int32_t> cand;
+  for (int32_t k = 0; k < K; ++k) {
+    const double* row = matrix + (size_t)k * (size_t)K;
+    cand.clear();
+    for (int32_t l = 0; l < K; ++l)
+      if (l != k && std::isfinite(row[l])) cand.push_back(l);
+    const size_t keep = std::min<size_t>((size_t)n, cand.size());
+    std::partial_sort(cand.begin(), cand.begin() + (std::ptrdiff_t)keep, cand.end(),
+                      [&](int32_t a, int32_t b) { return row[a] > row[b] || (row[a] == row[b] && a < b); });
+    for (int32_t i = 0; i < n; ++i) {
+      const bool has = (size_t)i < keep;
+      ids[(size_t)k * n + i] = has ? cand[(size_t)i] : -1;
+      values[(size_t)k * n + i] = has ? row[cand[(size_t)i]] : std::numeric_limits<double>::quiet_NaN();
+    }
+  }
+}
+
+std::string topicCorrelationsFormat(int32_t K, int32_t n, const int32_t* ids, const double* values) {
+  std::string out = "#topic partner value\n";
+  for (int32_t k = 0; k < K; ++k)
+    for (int32_t i = 0; i < n; ++i) {
+      const size_t at = (size_t)k * n + i;
+      if (ids[at] < 0) break;
+      out += std::to_string(k) + " " + std::to_string(ids[at]) + " " + java_double(values[at]) + "\n";
+    }
+  return out;
+}
+
+void ParallelTopicModel::topicCooccurrence(int64_t min_tokens, int32_t min_count, double min_prop, int64_t* docs_used,
+                                           int64_t* tokens, int64_t* present, int64_t* codocs, int64_t* overlap,
+                                           int64_t* product) {
+  checkCooccurrence(min_tokens, min_count, min_prop);
+  if (!docs_used || !tokens || !present)
+    raise(LDA_ERR_INVALID_ARG, "null output (docs_used, tokens and present are required)");
+  ensureShards();
+  const size_t G = shards_->ctx.size(), K = (size_t)K_, cells = K * K;
+  check(lda_topic_cooccurrence(shards_->ctx[0], min_tokens, min_count, min_prop, docs_used, tokens, present, codocs,
+                               overlap, product),
+        "lda_topic_cooccurrence");
+  if (G == 1) return;
+  // the other shards one at a time into a buffer of one shard's size
+  int64_t* outs[3] = {codocs, overlap, product};
+  std::vector<int64_t> head(2 * K), tabs[3];
+  for (int t = 0; t < 3; ++t)
+    if (outs[t]) tabs[t].resize(cells);
+  for (size_t g = 1; g < G; ++g) {
+    int64_t used = 0;
+    check(lda_topic_cooccurrence(shards_->ctx[g], min_tokens, min_count, min_prop, &used, head.data(),
+                                 head.data() + K, outs[0] ? tabs[0].data() : nullptr,
+                                 outs[1] ? tabs[1].data() : nullptr, outs[2] ? tabs[2].data() : nullptr),
+          "lda_topic_cooccurrence");
+    *docs_used += used;
+    for (size_t k = 0; k < K; ++k) {
+      tokens[k] += head[k];
+      present[k] += head[K + k];
+    }
+    for (int t = 0; t < 3; ++t)
+      if (outs[t])
+        for (size_t i = 0; i < cells; ++i) outs[t][i] += tabs[t][i];
+  }
+}
+
+void ParallelTopicModel::topicCorrelations(int32_t measure, int64_t min_tokens, int32_t min_count, double min_prop,
+                                           double* out) {
+  checkMeasure(measure);
+  checkCooccurrence(min_tokens, min_count, min_prop);
+  if (!out) raise(LDA_ERR_INVALID_ARG, "null output");
+  const size_t K = (size_t)K_;
+  const int32_t kind = correlationTable(measure);
+  int64_t used = 0;
+  std::vector<int64_t> tokens(K), present(K), table(K * K);
+  topicCooccurrence(min_tokens, min_count, min_prop, &used, tokens.data(), present.data(),
+                    kind == LDATM_COOC_CODOCS ? table.data() : nullptr,
+                    kind == LDATM_COOC_OVERLAP ? table.data() : nullptr,
+                    kind == LDATM_COOC_PRODUCT ? table.data() : nullptr);
+  topicCorrelationFinish(measure, K_, used, tokens.data(), present.data(), kind, table.data(), out);
+}
+
+void ParallelTopicModel::topicPartners(int32_t measure, int64_t min_tokens, int32_t min_count, double min_prop,
+                                       int32_t n, int32_t* ids, double* values) {
+  checkMeasure(measure);
+  checkCooccurrence(min_tokens, min_count, min_prop);
+  if (n < 1) raise(LDA_ERR_INVALID_ARG, "n must be at least 1");
+  if (!ids || !values) raise(LDA_ERR_INVALID_ARG, "null output");
+  std::vector<double> matrix((size_t)K_ * (size_t)K_);
+  topicCorrelations(measure, min_tokens, min_count, min_prop, matrix.data());
+  topicPartnersSelect(K_, n, matrix.data(), ids, values);
+}
+
+std::string ParallelTopicModel::topicCorrelationsText(int32_t measure, int32_t n, int64_t min_tokens,
+                                                      int32_t min_count, double min_prop) {
+  checkMeasure(measure);
+  checkCooccurrence(min_tokens, min_count, min_prop);
+  if (n < 1) raise(LDA_ERR_INVALID_ARG, "n must be at least 1");
+  const size_t cells = (size_t)K_ * (size_t)n;
+  std::vector<int32_t> ids(cells);
+  std::vector<double> values(cells);
+  topicPartners(measure, min_tokens, min_count, min_prop, n, ids.data(), values.data());
+  return topicCorrelationsFormat(K_, n, ids.data(), values.data());
+}
+
 namespace {
 // Mallet's TopicModelDiagnostics thresholds (its DEFAULT_DOC_PROPORTIONS)
 constexpr double DIAG_PROPS[LDATM_DIAG_PROPS] = {0.01, 0.02, 0.05, 0.1, 0.2, 0.3, 0.5};
@@ -2619,6 +2814,66 @@ lda_status ldatm_topic_phrases_bound(int32_t K, int32_t n, int32_t shards, const
     return LDA_ERR_INVALID_ARG;
   }
   return guard([&] { lda_host::topicPhrasesBound(K, n, shards, shard_counts, totals, bound, proven); });
+}
+
+lda_status ldatm_topic_cooccurrence(ldatm* m, int64_t min_tokens, int32_t min_count, double min_prop,
+                                    int64_t* docs_used, int64_t* tokens, int64_t* present, int64_t* codocs,
+                                    int64_t* overlap, int64_t* product) {
+  TM_CHECK(m);
+  return guard([&] {
+    m->model.topicCooccurrence(min_tokens, min_count, min_prop, docs_used, tokens, present, codocs, overlap, product);
+  });
+}
+
+lda_status ldatm_topic_correlation_finish(int32_t measure, int32_t K, int64_t docs_used, const int64_t* tokens,
+                                          const int64_t* present, int32_t table_kind, const int64_t* table,
+                                          double* out) {
+  return guard([&] {
+    lda_host::topicCorrelationFinish(measure, K, docs_used, tokens, present, table_kind, table, out);
+  });
+}
+
+lda_status ldatm_topic_correlations(ldatm* m, int32_t measure, int64_t min_tokens, int32_t min_count,
+                                    double min_prop, double* out) {
+  TM_CHECK(m);
+  return guard([&] { m->model.topicCorrelations(measure, min_tokens, min_count, min_prop, out); });
+}
+
+lda_status ldatm_topic_partners(ldatm* m, int32_t measure, int64_t min_tokens, int32_t min_count, double min_prop,
+                                int32_t n, int32_t* ids, double* values) {
+  TM_CHECK(m);
+  return guard([&] { m->model.topicPartners(measure, min_tokens, min_count, min_prop, n, ids, values); });
+}
+
+lda_status ldatm_topic_partners_select(int32_t K, int32_t n, const double* matrix, int32_t* ids, double* values) {
+  return guard([&] { lda_host::topicPartnersSelect(K, n, matrix, ids, values); });
+}
+
+lda_status ldatm_topic_correlations_text(ldatm* m, int32_t measure, int32_t n, int64_t min_tokens,
+                                         int32_t min_count, double min_prop, char* buf, size_t cap, size_t* len) {
+  TM_CHECK(m);
+  std::string s;
+  lda_status st = guard([&] { s = m->model.topicCorrelationsText(measure, n, min_tokens, min_count, min_prop); });
+  return st ? st : copy_text(s, buf, cap, len);
+}
+
+lda_status ldatm_print_topic_correlations(ldatm* m, const char* path, int32_t measure, int32_t n,
+                                          int64_t min_tokens, int32_t min_count, double min_prop) {
+  TM_CHECK(m);
+  std::string s;
+  lda_status st = guard([&] { s = m->model.topicCorrelationsText(measure, n, min_tokens, min_count, min_prop); });
+  return st ? st : write_file(path, s);
+}
+
+lda_status ldatm_topic_correlations_format(int32_t K, int32_t n, const int32_t* ids, const double* values,
+                                           char* buf, size_t cap, size_t* len) {
+  if (K < 1 || n < 1 || !ids || !values) {
+    g_tm_error = "bad argument";
+    return LDA_ERR_INVALID_ARG;
+  }
+  std::string s;
+  lda_status st = guard([&] { s = lda_host::topicCorrelationsFormat(K, n, ids, values); });
+  return st ? st : copy_text(s, buf, cap, len);
 }
 
 lda_status ldatm_save(ldatm* m, const char* path) {

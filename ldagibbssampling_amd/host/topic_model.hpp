@@ -68,6 +68,17 @@ std::string topicPhrasesFormat(int32_t K, int32_t n, int32_t max_len, const int3
                                const int32_t* lengths, const int64_t* counts,
                                const std::function<std::string(int32_t)>& name);
 
+// Topic co-occurrence, host only: the table a measure needs
+// (LDATM_COOC_*, -1 for an unknown measure), the K x K matrix of a measure
+// from lda_topic_cooccurrence's integers, each topic's n strongest other
+// topics from a matrix (value descending, then smaller id, non-finite values
+// left out, -1 / NaN past the last), and the partners' text.
+int32_t correlationTable(int32_t measure);
+void topicCorrelationFinish(int32_t measure, int32_t K, int64_t docs_used, const int64_t* tokens,
+                            const int64_t* present, int32_t table_kind, const int64_t* table, double* out);
+void topicPartnersSelect(int32_t K, int32_t n, const double* matrix, int32_t* ids, double* values);
+std::string topicCorrelationsFormat(int32_t K, int32_t n, const int32_t* ids, const double* values);
+
 class ParallelTopicModel {
  public:
   ParallelTopicModel(int32_t num_topics, double alpha_sum, double beta);
@@ -181,6 +192,18 @@ class ParallelTopicModel {
                     int64_t* skipped_long, int32_t* proven);
   // topicPhrases as text: "#topic rank count phrase", then "topic rank count w1 w2 ..."
   std::string topicPhrasesText(int32_t n, int32_t min_len, int32_t max_len, int32_t min_count);
+
+  // lda_topic_cooccurrence on every shard, summed (integers: exact); the
+  // matrix of one measure, counting only the table it needs; each topic's n
+  // strongest partners by it; the partners as text.  The arguments are
+  // checked before any shard is built.
+  void topicCooccurrence(int64_t min_tokens, int32_t min_count, double min_prop, int64_t* docs_used,
+                         int64_t* tokens, int64_t* present, int64_t* codocs, int64_t* overlap, int64_t* product);
+  void topicCorrelations(int32_t measure, int64_t min_tokens, int32_t min_count, double min_prop, double* out);
+  void topicPartners(int32_t measure, int64_t min_tokens, int32_t min_count, double min_prop, int32_t n,
+                     int32_t* ids, double* values);
+  std::string topicCorrelationsText(int32_t measure, int32_t n, int64_t min_tokens, int32_t min_count,
+                                    double min_prop);
 
   // ---- topic diagnostics --------------------------------
   // lda_topic_codocuments on every shard with the caller's lists, summed in

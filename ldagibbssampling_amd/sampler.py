@@ -553,6 +553,28 @@ class GibbsSampler:
                                              off.ctypes.data, flat.ctypes.data, cnt.ctypes.data), "lda_phrase_counts")
         return cnt
 
+    def topic_cooccurrence(self, stats=capi.TOPIC_COOC_STATS, min_tokens: int = 10, min_count: int = 2,
+                           min_prop: float = 0.05) -> dict:
+        """lda_topic_cooccurrence: which topics share this shard's documents,
+        counted on the device from z.  A document is used with at least
+        min_tokens tokens; topic k is present in it with n_dk >= min_count and
+        n_dk >= min_prop * L_d.  Returns a dict: "docs_used" (int), "tokens"
+        [K] and "present" [K] (int64), and of "codocs" / "overlap" / "product"
+        ([K, K] int64: documents with both present, sum of min(n_dk, n_dl), sum
+        of n_dk n_dl) those named in stats; only they are counted."""
+        stats = capi.topic_cooc_stats(stats)
+        min_tokens, min_count, min_prop = capi.topic_cooc_thresholds(min_tokens, min_count, min_prop)
+        used = C.c_int64()
+        out = {"tokens": np.zeros(self.K, np.int64), "present": np.zeros(self.K, np.int64)}
+        for s in stats:
+            out[s] = np.zeros((self.K, self.K), np.int64)
+        tabs = [out[s].ctypes.data if s in out else None for s in capi.TOPIC_COOC_STATS]
+        capi.check(self._L.lda_topic_cooccurrence(self._h, min_tokens, min_count, min_prop, C.byref(used),
+                                                  out["tokens"].ctypes.data, out["present"].ctypes.data, *tabs),
+                   "lda_topic_cooccurrence")
+        out["docs_used"] = int(used.value)
+        return out
+
     def _word_lists(self, word_ids):
         """(ids[K, n] int32, n) of K word lists, -1 = an empty slot."""
         ids = np.ascontiguousarray(word_ids, dtype=np.int32)

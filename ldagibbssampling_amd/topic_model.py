@@ -109,6 +109,15 @@ TM_SIGNATURES = {
     "ldatm_topic_phrases_format": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_size_t,
                                           C.POINTER(C.c_size_t)]),
     "ldatm_topic_phrases_bound": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "ldatm_topic_cooccurrence": (_i32, [_vp, C.c_int64, _i32, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ldatm_topic_correlation_finish": (_i32, [_i32, _i32, C.c_int64, _vp, _vp, _i32, _vp, _vp]),
+    "ldatm_topic_correlations": (_i32, [_vp, _i32, C.c_int64, _i32, C.c_double, _vp]),
+    "ldatm_topic_partners": (_i32, [_vp, _i32, C.c_int64, _i32, C.c_double, _i32, _vp, _vp]),
+    "ldatm_topic_partners_select": (_i32, [_i32, _i32, _vp, _vp, _vp]),
+    "ldatm_topic_correlations_text": (_i32, [_vp, _i32, _i32, C.c_int64, _i32, C.c_double, _vp, C.c_size_t,
+                                             C.POINTER(C.c_size_t)]),
+    "ldatm_print_topic_correlations": (_i32, [_vp, C.c_char_p, _i32, _i32, C.c_int64, _i32, C.c_double]),
+    "ldatm_topic_correlations_format": (_i32, [_i32, _i32, _vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "ldatm_save": (_i32, [_vp, C.c_char_p]),
     "ldatm_load": (_i32, [C.POINTER(_vp), C.c_char_p]),
     "ldatm_infer": (_i32, [_vp, C.c_int64, _i64p, _vp, _i32, _i32, _i32, C.c_uint64, _f64p]),
@@ -322,6 +331,80 @@ class TopicPhrases:
     def __init__(self, phrases, wordIds, counts, first, runs, distinct, skippedLong, proven):
         self.phrases, self.wordIds, self.counts, self.first = phrases, wordIds, counts, first
         self.runs, self.distinct, self.skippedLong, self.proven = runs, distinct, skippedLong, proven
+
+
+# LDATM_CORR_* / LDATM_COOC_* of lda_topic_model.h, and the table each measure takes
+CORR_MEASURES = {"pmi": 0, "npmi": 1, "jaccard": 2, "overlap": 3, "cosine": 4, "pearson": 5}
+COOC_TABLES = {"codocs": 0, "overlap": 1, "product": 2}
+MEASURE_TABLE = {"pmi": "codocs", "npmi": "codocs", "jaccard": "codocs", "overlap": "overlap",
+                 "cosine": "product", "pearson": "product"}
+
+
+def correlation_measure(measure) -> str:
+    """A measure of topic co-occurrence by name."""
+    if measure not in CORR_MEASURES:
+        raise ValueError(f"unknown measure {measure!r}: one of {tuple(CORR_MEASURES)}")
+    return measure
+
+
+def topic_correlation_finish(measure, docs_used, tokens, present, table, kind=None) -> np.ndarray:
+    """ldatm_topic_correlation_finish (host only, no device): the float64
+    [K, K] matrix of a measure ("pmi", "npmi", "jaccard" from codocs; "overlap"
+    from overlap; "cosine", "pearson" from product) out of
+    topic_cooccurrence's integers.  kind names the table that `table` is
+    (None: the measure's own); a wrong one is an error."""
+    measure = correlation_measure(measure)
+    kind = MEASURE_TABLE[measure] if kind is None else kind
+    if kind not in COOC_TABLES:
+        raise ValueError(f"unknown table {kind!r}: one of {tuple(COOC_TABLES)}")
+    tok = np.ascontiguousarray(tokens, np.int64)
+    pre = np.ascontiguousarray(present, np.int64)
+    tab = np.ascontiguousarray(table, np.int64)
+    K = tok.shape[0] if tok.ndim == 1 else -1
+    if K < 1 or pre.shape != (K,) or tab.shape != (K, K):
+        raise ValueError("tokens and present must be [K] and table [K, K]")
+    out = np.zeros((K, K), np.float64)
+    _check(load_tm().ldatm_topic_correlation_finish(CORR_MEASURES[measure], K, int(docs_used), tok.ctypes.data,
+                                                    pre.ctypes.data, COOC_TABLES[kind], tab.ctypes.data,
+                                                    out.ctypes.data), "ldatm_topic_correlation_finish")
+    return out
+
+
+def topic_partners_select(matrix, n: int):
+    """ldatm_topic_partners_select (host only): per row k of a [K, K] matrix
+    the n columns l != k with the largest finite values, larger first, equal
+    values by smaller id.  Returns (ids int32 [K, n], values float64 [K, n]),
+    -1 / NaN past the last."""
+    mat = np.ascontiguousarray(matrix, np.float64)
+    n = int(n)
+    if mat.ndim != 2 or mat.shape[0] != mat.shape[1] or mat.shape[0] < 1:
+        raise ValueError("matrix must be [K, K]")
+    if n < 1:
+        raise ValueError("n must be at least 1")
+    K = mat.shape[0]
+    ids = np.zeros((K, n), np.int32)
+    values = np.zeros((K, n), np.float64)
+    _check(load_tm().ldatm_topic_partners_select(K, n, mat.ctypes.data, ids.ctypes.data, values.ctypes.data),
+           "ldatm_topic_partners_select")
+    return ids, values
+
+
+def format_topic_correlations(ids, values) -> str:
+    """ldatm_topic_correlations_format (host only): printTopicCorrelations'
+    text from [K, n] partner ids and values."""
+    ids = np.ascontiguousarray(ids, np.int32)
+    values = np.ascontiguousarray(values, np.float64)
+    if ids.ndim != 2 or values.shape != ids.shape or ids.size == 0:
+        raise ValueError("ids and values must be [K, n] arrays of one shape")
+    K, n = ids.shape
+    L = load_tm()
+    size = C.c_size_t()
+    args = (K, n, ids.ctypes.data, values.ctypes.data)
+    _check(L.ldatm_topic_correlations_format(*args, None, 0, C.byref(size)), "ldatm_topic_correlations_format")
+    buf = C.create_string_buffer(size.value + 1)
+    _check(L.ldatm_topic_correlations_format(*args, buf, size.value + 1, C.byref(size)),
+           "ldatm_topic_correlations_format")
+    return buf.value.decode()
 
 
 class Alphabet:
@@ -839,6 +922,75 @@ class ParallelTopicModel:
                    for k in range(self.numTopics)]
         return TopicPhrases(phrases, ids, cnt, first, runs, distinct, skipped, proven)
 
+    # ------------------------------- topic co-occurrence in documents
+    def topicCooccurrence(self, stats=capi.TOPIC_COOC_STATS, minTokens: int = 10, minCount: int = 2,
+                          minProp: float = 0.05) -> dict:
+        """ldatm_topic_cooccurrence: which topics share documents, counted on
+        the device from z and summed over the shards.  A document is used with
+        at least minTokens tokens; topic k is present in it with n_dk >=
+        minCount and n_dk >= minProp * L_d (jsLDA's defaults).  Returns a dict:
+        "docs_used" (int), "tokens" [K] and "present" [K] (int64), and of
+        "codocs" / "overlap" / "product" ([K, K] int64: documents with both
+        present, sum of min(n_dk, n_dl), sum of n_dk n_dl) those named in
+        stats; only they are counted."""
+        stats = capi.topic_cooc_stats(stats)
+        thr = capi.topic_cooc_thresholds(minTokens, minCount, minProp)
+        K = self.numTopics
+        used = C.c_int64()
+        out = {"tokens": np.zeros(K, np.int64), "present": np.zeros(K, np.int64)}
+        for s in stats:
+            out[s] = np.zeros((K, K), np.int64)
+        tabs = [out[s].ctypes.data if s in out else None for s in capi.TOPIC_COOC_STATS]
+        _check(self._L.ldatm_topic_cooccurrence(self._h, *thr, C.byref(used), out["tokens"].ctypes.data,
+                                                out["present"].ctypes.data, *tabs), "topicCooccurrence")
+        out["docs_used"] = int(used.value)
+        return out
+
+    def topicCorrelations(self, measure="npmi", minTokens: int = 10, minCount: int = 2,
+                          minProp: float = 0.05) -> np.ndarray:
+        """ldatm_topic_correlations: the float64 [K, K] matrix of a measure of
+        co-occurrence in documents -- "pmi", "npmi", "jaccard" (documents with
+        both topics present), "overlap" (shared tokens), "cosine", "pearson"
+        (of the documents' topic counts) -- counting only the table it needs."""
+        m = CORR_MEASURES[correlation_measure(measure)]
+        thr = capi.topic_cooc_thresholds(minTokens, minCount, minProp)
+        out = np.zeros((self.numTopics, self.numTopics), np.float64)
+        _check(self._L.ldatm_topic_correlations(self._h, m, *thr, out.ctypes.data), "topicCorrelations")
+        return out
+
+    def topicPartners(self, n: int = 5, measure="npmi", minTokens: int = 10, minCount: int = 2,
+                      minProp: float = 0.05):
+        """ldatm_topic_partners: per topic its n strongest other topics by
+        topicCorrelations(measure): (ids int32 [K, n], values float64 [K, n]),
+        larger value first, equal values by smaller id, non-finite values left
+        out, -1 / NaN past the last."""
+        n = int(n)
+        if n < 1:
+            raise ValueError("n must be at least 1")
+        m = CORR_MEASURES[correlation_measure(measure)]
+        thr = capi.topic_cooc_thresholds(minTokens, minCount, minProp)
+        ids = np.zeros((self.numTopics, n), np.int32)
+        values = np.zeros((self.numTopics, n), np.float64)
+        _check(self._L.ldatm_topic_partners(self._h, m, *thr, n, ids.ctypes.data, values.ctypes.data),
+               "topicPartners")
+        return ids, values
+
+    def getTopicPartners(self, n: int = 5, measure="npmi", minTokens: int = 10, minCount: int = 2,
+                         minProp: float = 0.05) -> list:
+        """Per topic a list of (topic, value), at most n long, strongest first."""
+        ids, values = self.topicPartners(n, measure, minTokens, minCount, minProp)
+        return [[(int(t), float(v)) for t, v in zip(ids[k], values[k]) if t >= 0] for k in range(self.numTopics)]
+
+    def topicGraph(self, measure="npmi", cutoff: float = 0.0, minTokens: int = 10, minCount: int = 2,
+                   minProp: float = 0.05) -> list:
+        """The edges (k, l, value), k < l, whose topicCorrelations(measure)
+        value is at least cutoff (a NaN never is), by ascending (k, l)."""
+        mat = self.topicCorrelations(measure, minTokens, minCount, minProp)
+        cutoff = float(cutoff)
+        with np.errstate(invalid="ignore"):
+            k, l = np.nonzero(np.triu(mat >= cutoff, 1))
+        return [(int(a), int(b), float(mat[a, b])) for a, b in zip(k, l)]
+
     # ------------------------------- topic distances (DESIGN 9g)
     def _other_model(self, other):
         """(native handle or None, K2) of the other side of a topic
@@ -1080,6 +1232,27 @@ class ParallelTopicModel:
     def printTopicPhrases(self, path, n: int = 10, minLength: int = 2, maxLength: int = 32, minCount: int = 1):
         _check(self._L.ldatm_print_topic_phrases(self._h, os.fsencode(path), int(n), int(minLength), int(maxLength),
                                                  int(minCount)), "printTopicPhrases")
+
+    def topicCorrelationsText(self, n: int = 5, measure="npmi", minTokens: int = 10, minCount: int = 2,
+                              minProp: float = 0.05) -> str:
+        """printTopicCorrelations' text: "#topic partner value", then per topic
+        and rank "topic partner value"."""
+        n = int(n)
+        if n < 1:
+            raise ValueError("n must be at least 1")
+        m = CORR_MEASURES[correlation_measure(measure)]
+        thr = capi.topic_cooc_thresholds(minTokens, minCount, minProp)
+        return self._text(self._L.ldatm_topic_correlations_text, m, n, *thr)
+
+    def printTopicCorrelations(self, path, n: int = 5, measure="npmi", minTokens: int = 10, minCount: int = 2,
+                               minProp: float = 0.05):
+        n = int(n)
+        if n < 1:
+            raise ValueError("n must be at least 1")
+        m = CORR_MEASURES[correlation_measure(measure)]
+        thr = capi.topic_cooc_thresholds(minTokens, minCount, minProp)
+        _check(self._L.ldatm_print_topic_correlations(self._h, os.fsencode(path), m, n, *thr),
+               "printTopicCorrelations")
 
     # ------------------------------------------------ checkpoint / resume
     def save(self, path):
