@@ -640,6 +640,98 @@ lda_status lda_topic_cooccurrence(lda_ctx* ctx, int64_t min_tokens, int32_t min_
  * atomics at every K (0 = the default, LDS up to LDA_TOPIC_COOC_LDS_TOPICS). */
 void lda_debug_topic_cooccurrence_global(int32_t on);
 
+/* lda_group_topics: how much of each group of documents is each topic, counted
+ * on the device from the shard's current z.  doc_group[d], a
+ * host array over THIS shard's documents, is document d's group in [-1, G);
+ * -1 leaves the document out.  n_dk is document d's count of topic k, L_d its
+ * length.  Used and present are lda_topic_cooccurrence's:
+ *   A document is USED when its group is >= 0 and L_d >= min_tokens
+ *   (min_tokens >= 1).
+ *   Topic k is PRESENT in d when n_dk >= min_count and
+ *       (double) n_dk >= min_prop * (double) L_d
+ *   (min_count >= 1, 0 <= min_prop <= 1; one fp64 product and one compare).
+ * Over the used documents of group g:
+ *   group_docs[g]    = their number
+ *   group_tokens[g]  = sum of L_d
+ *   tokens[g*K + k]  = sum of n_dk
+ *   present[g*K + k] = documents in which k is present
+ *   shares[g*K + k]  = sum over d of floor(n_dk * 2^32 / L_d), one unsigned
+ *                      64-bit integer division per nonzero (document, topic)
+ * shares / (2^32 group_docs) is the document-weighted mean proportion of the
+ * topic in the group, short by less than 2^-32 per document; it is kept in
+ * fixed point so that every output is a function of z alone: 64-bit integer
+ * adds only, whatever the grid and the order of arrival.  present and shares
+ * are each requested by a non-NULL pointer, and only the requested tables are
+ * allocated and accumulated.  One wave per document.  When group_docs,
+ * group_tokens, the requested tables and the block's four wave histograms and
+ * lists (24 Kp bytes) fit 64 KiB of LDS, a block accumulates them there and
+ * adds its nonzero cells to global memory once; otherwise every add is a
+ * global atomic (lda_group_topics_path says which).
+ * Errors, checked on the host in this order before any device work:
+ * LDA_ERR_INVALID_ARG for a NULL ctx, G < 1, a NULL group_docs / group_tokens
+ * / tokens, min_tokens < 1, min_count < 1, min_prop outside [0, 1] or NaN, a
+ * NULL doc_group with D > 0, a group id outside [-1, G) (the message names the
+ * first such document); LDA_ERR_STATE with a pending delta (call lda_apply
+ * first); LDA_ERR_UNSUPPORTED when G * K > LDA_GROUP_TOPICS_MAX_CELLS (2 GiB
+ * per table) or when shares is requested with D >= 2^31 (a cell holds fewer
+ * than 2^31 shares of at most 2^32).  D = 0 succeeds with zeros.  Changes no
+ * state of the context.  Device scratch is grow-only and kept by the context:
+ * 4 D bytes and 8 (2 G + tables G K) bytes, all of the latter copied to the
+ * host.  Waits once for the context's stream. */
+#define LDA_GROUP_TOPICS_MAX_CELLS (1 << 28)
+lda_status lda_group_topics(lda_ctx* ctx, const int32_t* doc_group /*[D]*/, int32_t G, int64_t min_tokens,
+                            int32_t min_count, double min_prop, int64_t* group_docs /*[G]*/,
+                            int64_t* group_tokens /*[G]*/, int64_t* tokens /*[G*K]*/,
+                            int64_t* present /*[G*K] or NULL*/, uint64_t* shares /*[G*K] or NULL*/);
+/* Host only: the path lda_group_topics takes for G groups, K topics and
+ * `tables` G x K tables (tokens and each requested one of present and shares:
+ * 1 to 3): 1 = LDS accumulation, 0 = global atomics, -1 = a bad argument
+ * (G < 1, K outside [1, LDA_MAX_TOPICS], tables outside [1, 3]).  *lds (may be
+ * NULL) gets the dynamic LDS bytes of a block on that path. */
+int32_t lda_group_topics_path(int32_t G, int32_t K, int32_t tables, int32_t* lds);
+/* Test and measurement hook: on != 0 makes lda_group_topics use global atomics
+ * at every shape (0 = the default, LDS where lda_group_topics_path says 1). */
+void lda_debug_group_topics_global(int32_t on);
+
+/* Sub-corpus topic words: each topic's top words inside a chosen set of
+ * documents only.  A
+ * context gets an optional sub-corpus table sub[V x Kp] of int32, allocated by
+ * the first lda_subcorpus_count, kept until lda_subcorpus_release (or
+ * lda_destroy) and never touched by sampling.  The table is a SNAPSHOT of z at
+ * the time of the count: later sweeps neither update nor invalidate it.
+ * lda_subcorpus_count: sub[w, k] becomes the number of tokens of word w with
+ * topic k in the documents of THIS shard whose byte of doc_mask (a host array
+ * [D]) is nonzero; accumulate = 0 zeroes the table first, accumulate != 0 adds
+ * to what it holds (a table allocated by this call starts from zero either
+ * way).  One wave per document; a masked-out document costs one load.  A cell
+ * is bounded by the model's global count of (w, k), so int32 holds it.
+ * LDA_ERR_INVALID_ARG for a NULL ctx or a NULL doc_mask with D > 0,
+ * LDA_ERR_STATE with a pending delta; a failed allocation is
+ * LDA_ERR_OUT_OF_MEMORY and leaves no table.  The table is complete when the
+ * call returns.
+ * lda_subcorpus_merge: sub(ctx) += sub(from), cell by cell; from is unchanged.
+ * This is how the shards of one model add up exactly: the top n of a sum is
+ * not a merge of the shards' top n, so the tables are added before selecting.
+ * LDA_ERR_INVALID_ARG for a NULL ctx or from, from == ctx, or contexts that
+ * differ in V or K; LDA_ERR_STATE with a pending delta on either or a missing
+ * table on either.  The shards of one model cannot overflow a cell; a sum
+ * above int32 between unrelated contexts wraps and is the caller's concern.
+ * On one device it is one elementwise add; between devices from's table comes
+ * over in chunks of a 64 MiB staging buffer by peer copies.
+ * lda_subcorpus_top_words: lda_top_words' definition, ordering and padding
+ * (count descending, equal counts by ascending word id, zero counts left out,
+ * -1 / 0 past the last) applied to sub by the same kernels; totals[k] is the
+ * sum of column k of sub (int64).  LDA_ERR_INVALID_ARG for a NULL ctx, n
+ * outside [1, LDA_TOP_WORDS_MAX] or a NULL output; LDA_ERR_STATE with a
+ * pending delta or without a table.
+ * lda_subcorpus_release: frees the table (no table: nothing to do).
+ * Each call waits once for the context's stream and changes nothing else. */
+lda_status lda_subcorpus_count(lda_ctx* ctx, const uint8_t* doc_mask /*[D]*/, int32_t accumulate);
+lda_status lda_subcorpus_merge(lda_ctx* ctx, lda_ctx* from);
+lda_status lda_subcorpus_top_words(lda_ctx* ctx, int32_t n, int32_t* word_ids /*[K*n]*/, int32_t* counts /*[K*n]*/,
+                                   int64_t* totals /*[K]*/);
+lda_status lda_subcorpus_release(lda_ctx* ctx);
+
 /* Relevance-ranked topic words, salient terms and word rows: what an LDAvis
  * view of a trained model shows, selected on the device from the global counts
  * this shard holds (the int32 nw rows, V x Kp, and nwsum), without the V x K
@@ -1100,7 +1192,10 @@ void lda_debug_fail_host_alloc(int32_t nth);
  * lda_debug_phrase_table_slots), then lda_relevant_words, lda_salient_words
  * and lda_word_rows (with their test hook lda_debug_relevance_slab_rows), then
  * lda_topic_cooccurrence (with its test hook
- * lda_debug_topic_cooccurrence_global) came later and only add symbols, so the
+ * lda_debug_topic_cooccurrence_global), then lda_group_topics (with
+ * lda_group_topics_path and its test hook lda_debug_group_topics_global) and
+ * lda_subcorpus_count, lda_subcorpus_merge, lda_subcorpus_top_words and
+ * lda_subcorpus_release came later and only add symbols, so the
  * version stays 8. */
 #define LDA_ABI_VERSION 8
 const char* lda_version(void);

@@ -481,6 +481,81 @@ lda_status ldatm_print_topic_correlations(ldatm* m, const char* path, int32_t me
 lda_status ldatm_topic_correlations_format(int32_t K, int32_t n, const int32_t* ids, const double* values,
                                            char* buf, size_t cap, size_t* len);
 
+/* Topics by document group: how the topics differ between groups of documents
+ * (years, sources, labels), and a topic's top words inside a group only
+ * (lda_group_topics and lda_subcorpus_* of lda_mi355x.h, which state the
+ * definitions; the question of jsLDA's time series and of stm's
+ * estimateEffect plots).
+ * ldatm_group_topics: lda_group_topics' outputs summed over the model's shards
+ * -- integer sums, so the result does not depend on the number of shards.
+ * doc_group[D] holds a group id in [-1, G) for every document of the model in
+ * its global order (-1 leaves the document out); each shard gets its slice.
+ * group_docs[G], group_tokens[G] and tokens[G*K] are required; present[G*K]
+ * and shares[G*K] are each counted only when the pointer is not NULL.
+ * ldatm_group_prevalence_finish (host only, no model and no device): a G x K
+ * matrix of doubles from those integers:
+ *   LDATM_GROUP_TOKENS     tokens_gk / group_tokens_g
+ *   LDATM_GROUP_DOCUMENTS  present_gk / group_docs_g           (needs present)
+ *   LDATM_GROUP_MEAN       shares_gk / (2^32 * group_docs_g)   (needs shares)
+ *   LDATM_GROUP_LIFT       log((tokens_gk / group_tokens_g) / (N_k / N)),
+ *                          N_k = sum over g of tokens_gk, N = sum over g of
+ *                          group_tokens_g
+ * Every integer becomes a double once, then one rounding per operation in the
+ * order written (mean's denominator is the product 4294967296.0 * (double)
+ * group_docs_g).  A value is NaN where a denominator (group_tokens_g,
+ * group_docs_g, N_k, N) is 0; lift is -inf where tokens_gk = 0 and no
+ * denominator is.  An unknown kind, or a kind without the table it needs, is
+ * LDA_ERR_INVALID_ARG with a message.
+ * ldatm_group_prevalence: counts only the table the kind needs, then finishes;
+ * out[G*K].
+ * ldatm_group_top_topics_select (host only): per group the n largest values
+ * of a G x K matrix, ldatm_topic_partners_select's rule: larger value first,
+ * equal values by smaller topic id, non-finite values left out; ids / values
+ * [G*n], -1 / NaN past the last.
+ * ldatm_group_topics_text / ldatm_print_group_topics: that selection of
+ * ldatm_group_prevalence's matrix as text, "#group topic value\n", then
+ * "<group> <topic> <value>\n" per group and rank (Java Double.toString);
+ * empty slots print nothing.  ldatm_group_topics_format: the text from the
+ * caller's G x n arrays (host only).
+ * ldatm_subcorpus_top_words: each topic's top n words inside the documents
+ * whose byte of doc_mask[D] (global order) is nonzero: every shard counts its
+ * slice (lda_subcorpus_count), the tables are added into the first shard's
+ * (lda_subcorpus_merge), which selects (lda_subcorpus_top_words: word_ids /
+ * counts [K*n] as ldatm_top_words gives them, totals[K] the topic's tokens in
+ * the sub-corpus), and the tables are released whatever the outcome.
+ * Errors, checked before any device work (a model without a GPU names its bad
+ * argument): LDA_ERR_INVALID_ARG for a NULL model, an unknown kind, G < 1, a
+ * NULL required output, min_tokens < 1, min_count < 1, min_prop outside [0, 1]
+ * or NaN, n < 1 (n outside [1, LDA_TOP_WORDS_MAX] for the words), a NULL
+ * doc_group / doc_mask with documents, a group id outside [-1, G) (the
+ * message names the first such document); LDA_ERR_UNSUPPORTED for G * K >
+ * LDA_GROUP_TOPICS_MAX_CELLS. */
+#define LDATM_GROUP_TOKENS 0
+#define LDATM_GROUP_DOCUMENTS 1
+#define LDATM_GROUP_MEAN 2
+#define LDATM_GROUP_LIFT 3
+lda_status ldatm_group_topics(ldatm* m, const int32_t* doc_group /*[D]*/, int32_t G, int64_t min_tokens,
+                              int32_t min_count, double min_prop, int64_t* group_docs /*[G]*/,
+                              int64_t* group_tokens /*[G]*/, int64_t* tokens /*[G*K]*/,
+                              int64_t* present /*[G*K] or NULL*/, uint64_t* shares /*[G*K] or NULL*/);
+lda_status ldatm_group_prevalence_finish(int32_t kind, int32_t G, int32_t K, const int64_t* group_docs,
+                                         const int64_t* group_tokens, const int64_t* tokens,
+                                         const int64_t* present /*or NULL*/, const uint64_t* shares /*or NULL*/,
+                                         double* out /*[G*K]*/);
+lda_status ldatm_group_prevalence(ldatm* m, const int32_t* doc_group /*[D]*/, int32_t G, int32_t kind,
+                                  int64_t min_tokens, int32_t min_count, double min_prop, double* out /*[G*K]*/);
+lda_status ldatm_group_top_topics_select(int32_t G, int32_t K, int32_t n, const double* matrix /*[G*K]*/,
+                                         int32_t* ids /*[G*n]*/, double* values /*[G*n]*/);
+lda_status ldatm_group_topics_text(ldatm* m, const int32_t* doc_group /*[D]*/, int32_t G, int32_t kind, int32_t n,
+                                   int64_t min_tokens, int32_t min_count, double min_prop, char* buf, size_t cap,
+                                   size_t* len);
+lda_status ldatm_print_group_topics(ldatm* m, const char* path, const int32_t* doc_group /*[D]*/, int32_t G,
+                                    int32_t kind, int32_t n, int64_t min_tokens, int32_t min_count, double min_prop);
+lda_status ldatm_group_topics_format(int32_t G, int32_t n, const int32_t* ids, const double* values, char* buf,
+                                     size_t cap, size_t* len);
+lda_status ldatm_subcorpus_top_words(ldatm* m, const uint8_t* doc_mask /*[D]*/, int32_t n,
+                                     int32_t* word_ids /*[K*n]*/, int32_t* counts /*[K*n]*/, int64_t* totals /*[K]*/);
+
 /* Relevance-ranked topic words, salient terms and word rows: what an LDAvis
  * view shows (lda_relevant_words, lda_salient_words and lda_word_rows of
  * lda_mi355x.h, which states the definitions).  They run on shard 0

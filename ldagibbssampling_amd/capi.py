@@ -65,6 +65,48 @@ def topic_cooc_thresholds(min_tokens, min_count, min_prop) -> tuple:
     if not 0.0 <= min_prop <= 1.0:
         raise ValueError("min_prop must be in [0, 1]")
     return min_tokens, min_count, min_prop
+# LDA_GROUP_TOPICS_MAX_CELLS of lda_mi355x.h: lda_group_topics takes G * K up to this
+GROUP_TOPICS_MAX_CELLS = 1 << 28
+# lda_group_topics' optional G x K tables, in the order of its arguments
+GROUP_TOPICS_STATS = ("present", "shares")
+
+
+def group_topics_stats(stats) -> tuple:
+    """The requested optional tables of lda_group_topics as a tuple of names,
+    in the call's order; a single name is accepted."""
+    if isinstance(stats, str):
+        stats = (stats,)
+    stats = tuple(stats)
+    for s in stats:
+        if s not in GROUP_TOPICS_STATS:
+            raise ValueError(f"unknown statistic {s!r}: one of {GROUP_TOPICS_STATS}")
+    return tuple(s for s in GROUP_TOPICS_STATS if s in stats)
+
+
+def group_ids(doc_group, D: int, G=None) -> tuple:
+    """(ids int32 [D], G) of lda_group_topics' doc_group, checked as the library
+    checks it: one id in [-1, G) per document; G = None takes the largest id
+    plus one (at least 1)."""
+    ids = np.ascontiguousarray(doc_group, dtype=np.int64)
+    if ids.shape != (int(D),):
+        raise ValueError(f"doc_group must hold one group id per document ({int(D)})")
+    G = max(1, int(ids.max()) + 1 if ids.size else 1) if G is None else int(G)
+    if G < 1:
+        raise ValueError("G must be at least 1")
+    bad = np.nonzero((ids < -1) | (ids >= G))[0]
+    if bad.size:
+        raise ValueError(f"doc_group[{int(bad[0])}] = {int(ids[bad[0]])} is outside [-1, G)")
+    return ids.astype(np.int32), G
+
+
+def doc_mask(mask, D: int) -> np.ndarray:
+    """lda_subcorpus_count's doc_mask: uint8 [D], nonzero = the document counts."""
+    m = np.asarray(mask)
+    if m.shape != (int(D),):
+        raise ValueError(f"mask must hold one entry per document ({int(D)})")
+    return np.ascontiguousarray(m != 0, dtype=np.uint8)
+
+
 # LDA_RELEVANCE_LAMBDAS_MAX / LDA_SALIENT_WORDS_MAX of lda_mi355x.h
 RELEVANCE_LAMBDAS_MAX = 128
 SALIENT_WORDS_MAX = 256
@@ -243,6 +285,13 @@ SIGNATURES = {
     "lda_debug_topic_docs_chunk_docs": (None, [C.c_int64]),
     "lda_topic_cooccurrence": (C.c_int32, [_vp, C.c_int64, C.c_int32, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lda_debug_topic_cooccurrence_global": (None, [C.c_int32]),
+    "lda_group_topics": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int64, C.c_int32, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "lda_group_topics_path": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "lda_debug_group_topics_global": (None, [C.c_int32]),
+    "lda_subcorpus_count": (C.c_int32, [_vp, _vp, C.c_int32]),
+    "lda_subcorpus_merge": (C.c_int32, [_vp, _vp]),
+    "lda_subcorpus_top_words": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp]),
+    "lda_subcorpus_release": (C.c_int32, [_vp]),
     "lda_relevant_words": (C.c_int32, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lda_salient_words": (C.c_int32, [_vp, C.c_int32, _vp, _vp, _vp, _vp]),
     "lda_word_rows": (C.c_int32, [_vp, C.c_int64, _vp, _vp, _vp]),

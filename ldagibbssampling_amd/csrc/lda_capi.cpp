@@ -252,6 +252,12 @@ static_assert(TOPIC_DOCS_WAVES <= lda::TOPIC_DOCS_MAX_SLABS, "the merge holds ev
 int64_t g_topic_docs_chunk = 0;   // lda_debug_topic_docs_chunk_docs (0: TOPIC_DOCS_CELLS / Kp)
 static_assert(LDA_TOPIC_COOC_LDS_TOPICS == lda::TOPIC_COOC_LDS_TOPICS, "the header states the kernel's boundary");
 int32_t g_topic_cooc_global = 0;  // lda_debug_topic_cooccurrence_global (1: global atomics at every K)
+int32_t g_group_topics_global = 0;  // lda_debug_group_topics_global (1: global atomics at every shape)
+// lda_group_topics: at most GROUP_TOPICS_MAX_CELLS cells per table (2 GiB)
+constexpr int64_t GROUP_TOPICS_MAX_CELLS = int64_t(1) << 28;
+static_assert(LDA_GROUP_TOPICS_MAX_CELLS == GROUP_TOPICS_MAX_CELLS, "the header states the limit");
+// lda_subcorpus_merge between devices: the staging chunk, in cells (64 MiB)
+constexpr int64_t SUBCORPUS_STAGE_CELLS = int64_t(1) << 24;
 // lda_topic_phrases / lda_phrase_counts: the table has the smallest power of
 // two of slots >= 2 * (N / min_len), between PHRASE_MIN_SLOTS and
 // PHRASE_MAX_SLOTS (12 bytes a slot: 3 GiB, and 4 more for the selection's
@@ -420,6 +426,19 @@ struct lda_ctx {
   // present [K], then the requested K x K tables
   unsigned long long* tc_buf = nullptr;
   size_t tc_cap = 0;
+  // lda_group_topics: grow-only scratch -- the documents' group ids [D] and
+  // group_docs [G], group_tokens [G], then the requested G x K tables
+  int32_t* gt_groups = nullptr;
+  unsigned long long* gt_buf = nullptr;
+  size_t gt_cap[2] = {};
+  // lda_subcorpus_*: the optional sub-corpus table [V x Kp] (null until the
+  // first lda_subcorpus_count, kept until lda_subcorpus_release; sampling never
+  // touches it), and grow-only scratch -- a call's mask [D], a merge's staging
+  // chunk, the column sums [K]
+  int32_t *sub = nullptr, *sub_stage = nullptr;
+  uint8_t* sub_mask = nullptr;
+  long long* sub_tot = nullptr;
+  size_t sub_cap[3] = {};
   // lda_relevant_words / lda_salient_words / lda_word_rows: grow-only scratch
   // -- N [1], the word totals and their logs [V], the distinctiveness [V], the
   // slab lists (keys, ids), the results of a pass (int32, int64, fp64), a
@@ -593,7 +612,8 @@ struct lda_ctx {
                     (void*)dg_ids, (void*)dg_table, (void*)dg_out, (void*)dg_shares,
                     (void*)cc_moff, (void*)cc_mem, (void*)cc_words, (void*)cc_out, (void*)cc_off,
                     (void*)td_rows, (void*)td_cnts, (void*)td_out, (void*)td_bits, (void*)td_ids, (void*)td_out_ids,
-                    (void*)tc_buf,
+                    (void*)tc_buf, (void*)gt_groups, (void*)gt_buf,
+                    (void*)sub, (void*)sub_stage, (void*)sub_mask, (void*)sub_tot,
                     (void*)rv_ntot, (void*)rv_tw, (void*)rv_out64, (void*)rv_logtp, (void*)rv_dist, (void*)rv_outd,
                     (void*)rv_keys, (void*)rv_ids, (void*)rv_out32, (void*)rv_list, (void*)rv_rows,
                     (void*)ph_keys, (void*)ph_u64, (void*)ph_sel_key, (void*)ph_cnts, (void*)ph_cand, (void*)ph_u32,
@@ -2679,12 +2699,11 @@ lda_status doc_readout(lda_ctx* c, int32_t m, int64_t doc_begin, int64_t M, cons
 
 }  // namespace
 
-lda_status lda_top_words(lda_ctx* c, int32_t n, int32_t* word_ids, int32_t* counts) {
-  return lda_abi::guarded([&]() -> lda_status {
-  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
-  if (n < 1 || n > LDA_TOP_WORDS_MAX) return fail(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_TOP_WORDS_MAX]");
-  if (!word_ids || !counts) return fail(LDA_ERR_INVALID_ARG, "null output");
-  if (c->pending) return fail(LDA_ERR_STATE, "top words with a pending delta: call lda_apply first");
+namespace {
+// lda_top_words' selection over a V x Kp int32 table of the context (nw, or the
+// sub-corpus table): the arguments are checked by the caller; queued on the
+// context's stream, which the caller waits for
+lda_status top_words_of(lda_ctx* c, const int32_t* table, int32_t n, int32_t* word_ids, int32_t* counts) {
   const size_t cells = (size_t)c->K * (size_t)n;
   if (c->V == 0) {
     std::fill(word_ids, word_ids + cells, -1);
@@ -2700,7 +2719,7 @@ lda_status lda_top_words(lda_ctx* c, int32_t n, int32_t* word_ids, int32_t* coun
   HIP_TRY(ro_need(c, c->ro_lists, (size_t)(slabs * c->Kp) * (size_t)n, 0));
   HIP_TRY(ro_need(c, c->ro_out, 2 * cells, 1));
   lda::TopWordsArgs a{};
-  a.nw = c->nw;
+  a.nw = table;
   a.V = c->V;
   a.K = c->K;
   a.Kp = c->Kp;
@@ -2713,7 +2732,18 @@ lda_status lda_top_words(lda_ctx* c, int32_t n, int32_t* word_ids, int32_t* coun
   HIP_TRY(lda::launch_top_words(a, c->stream));
   HIP_TRY(hipMemcpyAsync(word_ids, a.ids, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(counts, a.counts, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LDA_OK;
+}
+}  // namespace
+
+lda_status lda_top_words(lda_ctx* c, int32_t n, int32_t* word_ids, int32_t* counts) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (n < 1 || n > LDA_TOP_WORDS_MAX) return fail(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_TOP_WORDS_MAX]");
+  if (!word_ids || !counts) return fail(LDA_ERR_INVALID_ARG, "null output");
+  if (c->pending) return fail(LDA_ERR_STATE, "top words with a pending delta: call lda_apply first");
+  if (lda_status s = top_words_of(c, c->nw, n, word_ids, counts); s != LDA_OK) return s;
+  if (c->V > 0) HIP_TRY(hipStreamSynchronize(c->stream));
   return LDA_OK;
   });
 }
@@ -3439,6 +3469,179 @@ lda_status lda_topic_cooccurrence(lda_ctx* c, int64_t min_tokens, int32_t min_co
   *docs_used = hd[0];
   std::copy(hd.begin() + 1, hd.begin() + 1 + (std::ptrdiff_t)K, tokens);
   std::copy(hd.begin() + 1 + (std::ptrdiff_t)K, hd.end(), present);
+  return LDA_OK;
+  });
+}
+
+void lda_debug_group_topics_global(int32_t on) { g_group_topics_global = on != 0; }
+
+int32_t lda_group_topics_path(int32_t G, int32_t K, int32_t tables, int32_t* lds) {
+  if (lds) *lds = 0;
+  if (G < 1 || K < 1 || K > LDA_MAX_TOPICS || tables < 1 || tables > 3) return -1;
+  const int64_t cells = 2 * (int64_t)G + (int64_t)tables * G * K;
+  const int64_t wave = (int64_t)lda::group_topics_wave_bytes(pad_topics(K));
+  const int64_t with_block = wave + cells * (int64_t)sizeof(unsigned long long);
+  const bool fits = with_block <= (int64_t)lda::GROUP_TOPICS_LDS_BYTES;
+  if (lds) *lds = (int32_t)(fits ? with_block : wave);
+  return fits ? 1 : 0;
+}
+
+lda_status lda_group_topics(lda_ctx* c, const int32_t* doc_group, int32_t G, int64_t min_tokens, int32_t min_count,
+                            double min_prop, int64_t* group_docs, int64_t* group_tokens, int64_t* tokens,
+                            int64_t* present, uint64_t* shares) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (G < 1) return fail(LDA_ERR_INVALID_ARG, "G must be at least 1");
+  if (!group_docs || !group_tokens || !tokens)
+    return fail(LDA_ERR_INVALID_ARG, "null output (group_docs, group_tokens and tokens are required)");
+  if (min_tokens < 1) return fail(LDA_ERR_INVALID_ARG, "min_tokens must be at least 1");
+  if (min_count < 1) return fail(LDA_ERR_INVALID_ARG, "min_count must be at least 1");
+  if (!(min_prop >= 0.0 && min_prop <= 1.0)) return fail(LDA_ERR_INVALID_ARG, "min_prop must be in [0, 1]");
+  if (c->D > 0 && !doc_group) return fail(LDA_ERR_INVALID_ARG, "null doc_group");
+  for (int64_t d = 0; d < c->D; ++d)
+    if (doc_group[d] < -1 || doc_group[d] >= G)
+      return fail(LDA_ERR_INVALID_ARG, "doc_group[" + std::to_string(d) + "] = " + std::to_string(doc_group[d]) +
+                                           " is outside [-1, G)");
+  if (c->pending) return fail(LDA_ERR_STATE, "group topics with a pending delta: call lda_apply first");
+  const int64_t gk = (int64_t)G * c->K;
+  if (gk > GROUP_TOPICS_MAX_CELLS)
+    return fail(LDA_ERR_UNSUPPORTED, "group topics: G x K above LDA_GROUP_TOPICS_MAX_CELLS");
+  if (shares && c->D >= (int64_t(1) << 31))
+    return fail(LDA_ERR_UNSUPPORTED, "group topics: shares with 2^31 documents or more");
+  const int ntab = 1 + (present != nullptr) + (shares != nullptr);
+  const size_t Gs = (size_t)G, cells = (size_t)gk, total = 2 * Gs + (size_t)ntab * cells;
+  if (c->D == 0) {
+    std::fill(group_docs, group_docs + Gs, (int64_t)0);
+    std::fill(group_tokens, group_tokens + Gs, (int64_t)0);
+    std::fill(tokens, tokens + cells, (int64_t)0);
+    if (present) std::fill(present, present + cells, (int64_t)0);
+    if (shares) std::fill(shares, shares + cells, (uint64_t)0);
+    return LDA_OK;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(grow_bytes(reinterpret_cast<void**>(&c->gt_groups), &c->gt_cap[0], (size_t)c->D * sizeof(int32_t)));
+  HIP_TRY(grow_bytes(reinterpret_cast<void**>(&c->gt_buf), &c->gt_cap[1], total * sizeof(unsigned long long)));
+  HIP_TRY(hipMemcpyAsync(c->gt_groups, doc_group, (size_t)c->D * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(c->gt_buf, 0, total * sizeof(unsigned long long), c->stream));
+  lda::GroupTopicsArgs a{};
+  a.z = c->z;
+  a.doc_off = c->doc_off;
+  a.doc_group = c->gt_groups;
+  a.D = c->D;
+  a.min_tokens = min_tokens;
+  a.min_prop = min_prop;
+  a.min_count = min_count;
+  a.K = c->K;
+  a.Kp = c->Kp;
+  a.G = G;
+  a.o_present = present ? (int64_t)(2 * Gs + cells) : -1;
+  a.o_shares = shares ? (int64_t)(2 * Gs + (size_t)(ntab - 1) * cells) : -1;
+  a.cells = (int64_t)total;
+  a.buf = c->gt_buf;
+  const int lds = !g_group_topics_global && lda_group_topics_path(G, c->K, ntab, nullptr) == 1;
+  const int blocks = (int)std::min<int64_t>((c->D + 3) / 4, (int64_t)c->cus * 8);
+  HIP_TRY(lda::launch_group_topics(a, blocks, lds, c->stream));
+  auto back = [&](void* dst, size_t first, size_t n) {
+    return hipMemcpyAsync(dst, c->gt_buf + first, sizeof(int64_t) * n, hipMemcpyDeviceToHost, c->stream);
+  };
+  HIP_TRY(back(group_docs, 0, Gs));
+  HIP_TRY(back(group_tokens, Gs, Gs));
+  HIP_TRY(back(tokens, 2 * Gs, cells));
+  if (present) HIP_TRY(back(present, (size_t)a.o_present, cells));
+  if (shares) HIP_TRY(back(shares, (size_t)a.o_shares, cells));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LDA_OK;
+  });
+}
+
+lda_status lda_subcorpus_count(lda_ctx* c, const uint8_t* doc_mask, int32_t accumulate) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (c->D > 0 && !doc_mask) return fail(LDA_ERR_INVALID_ARG, "null doc_mask");
+  if (c->pending) return fail(LDA_ERR_STATE, "sub-corpus count with a pending delta: call lda_apply first");
+  HIP_TRY(hipSetDevice(c->device));
+  // a table of no cells (V = 0) still exists: one cell stands for it
+  const size_t bytes = std::max<size_t>(1, (size_t)c->V * (size_t)c->Kp) * sizeof(int32_t);
+  const bool fresh = !c->sub;
+  if (fresh) {
+    void* table = nullptr;
+    HIP_TRY(hipMalloc(&table, bytes));   // a failure leaves no table
+    c->sub = static_cast<int32_t*>(table);
+  }
+  if (fresh || !accumulate) HIP_TRY(hipMemsetAsync(c->sub, 0, bytes, c->stream));
+  if (c->D > 0) {
+    HIP_TRY(grow_bytes(reinterpret_cast<void**>(&c->sub_mask), &c->sub_cap[0], (size_t)c->D));
+    HIP_TRY(hipMemcpyAsync(c->sub_mask, doc_mask, (size_t)c->D, hipMemcpyHostToDevice, c->stream));
+    const int blocks = (int)std::min<int64_t>((c->D + 3) / 4, (int64_t)c->cus * 8);
+    HIP_TRY(lda::launch_subcorpus_count(c->z, c->words, c->doc_off, c->sub_mask, c->D, c->Kp, c->sub, blocks,
+                                        c->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));   // the table is complete when the call returns: a merge may read it
+  return LDA_OK;
+  });
+}
+
+lda_status lda_subcorpus_merge(lda_ctx* c, lda_ctx* from) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (!from) return fail(LDA_ERR_INVALID_ARG, "null from");
+  if (from == c) return fail(LDA_ERR_INVALID_ARG, "sub-corpus merge of a context into itself");
+  if (from->V != c->V || from->K != c->K)
+    return fail(LDA_ERR_INVALID_ARG, "sub-corpus merge: the contexts differ in V or K");
+  if (c->pending || from->pending)
+    return fail(LDA_ERR_STATE, "sub-corpus merge with a pending delta: call lda_apply first");
+  if (!c->sub || !from->sub)
+    return fail(LDA_ERR_STATE, "sub-corpus merge without a table: call lda_subcorpus_count on both contexts first");
+  const int64_t cells = (int64_t)c->V * c->Kp;
+  HIP_TRY(hipSetDevice(c->device));
+  if (from->device == c->device) {
+    HIP_TRY(lda::launch_subcorpus_add(c->sub, from->sub, cells, c->stream));
+  } else {
+    // the other device's table comes over in chunks of a bounded staging buffer
+    const int64_t chunk = std::min<int64_t>(cells, SUBCORPUS_STAGE_CELLS);
+    HIP_TRY(grow_bytes(reinterpret_cast<void**>(&c->sub_stage), &c->sub_cap[1], (size_t)chunk * sizeof(int32_t)));
+    for (int64_t i = 0; i < cells; i += chunk) {
+      const int64_t n = std::min<int64_t>(chunk, cells - i);
+      HIP_TRY(hipMemcpyPeerAsync(c->sub_stage, c->device, from->sub + i, from->device, (size_t)n * sizeof(int32_t),
+                                 c->stream));
+      HIP_TRY(lda::launch_subcorpus_add(c->sub + i, c->sub_stage, n, c->stream));
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LDA_OK;
+  });
+}
+
+lda_status lda_subcorpus_top_words(lda_ctx* c, int32_t n, int32_t* word_ids, int32_t* counts, int64_t* totals) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (n < 1 || n > LDA_TOP_WORDS_MAX) return fail(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_TOP_WORDS_MAX]");
+  if (!word_ids || !counts || !totals) return fail(LDA_ERR_INVALID_ARG, "null output");
+  if (c->pending) return fail(LDA_ERR_STATE, "sub-corpus top words with a pending delta: call lda_apply first");
+  if (!c->sub) return fail(LDA_ERR_STATE, "sub-corpus top words without a table: call lda_subcorpus_count first");
+  if (lda_status s = top_words_of(c, c->sub, n, word_ids, counts); s != LDA_OK) return s;
+  if (c->V == 0) {
+    std::fill(totals, totals + c->K, (int64_t)0);
+    return LDA_OK;
+  }
+  const size_t tb = (size_t)c->K * sizeof(long long);
+  HIP_TRY(grow_bytes(reinterpret_cast<void**>(&c->sub_tot), &c->sub_cap[2], tb));
+  HIP_TRY(hipMemsetAsync(c->sub_tot, 0, tb, c->stream));
+  HIP_TRY(lda::launch_subcorpus_totals(c->sub, c->V, c->K, c->Kp, c->sub_tot, c->stream));
+  HIP_TRY(hipMemcpyAsync(totals, c->sub_tot, tb, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LDA_OK;
+  });
+}
+
+lda_status lda_subcorpus_release(lda_ctx* c) {
+  return lda_abi::guarded([&]() -> lda_status {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (!c->sub) return LDA_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  HIP_TRY(hipFree(c->sub));
+  c->sub = nullptr;
   return LDA_OK;
   });
 }

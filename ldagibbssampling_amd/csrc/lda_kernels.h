@@ -700,5 +700,40 @@ struct TopicCoocArgs {
   unsigned long long* product;   // [K * K] or NULL
 };
 hipError_t launch_topic_cooc(const TopicCoocArgs& a, int blocks, int lds, hipStream_t st);
+// lda_group_topics: k_group_topics, one wave per document with a
+// group id >= 0 and at least min_tokens tokens, builds the document's topic
+// counts and the list of its distinct topics as k_topic_cooc does and adds, to
+// row g of the tables, n_dk (tokens), 1 when the topic is present (present) and
+// floor(n_dk 2^32 / L_d) (shares); 1 and L_d to group_docs[g], group_tokens[g].
+// buf = group_docs [G], group_tokens [G], tokens [G K], then present [G K] and
+// shares [G K] when requested; o_present / o_shares are their first cells (-1:
+// not requested) and cells the length of buf, which must be zero before the
+// launch.  With lds != 0 a block keeps a copy of buf in 64-bit LDS cells behind
+// the four waves' histograms and lists (group_topics_wave_bytes) and adds its
+// nonzero cells once; the whole must fit GROUP_TOPICS_LDS_BYTES, the default
+// dynamic LDS limit.  Otherwise every add is a global 64-bit integer atomic.
+constexpr size_t GROUP_TOPICS_LDS_BYTES = 65536;
+inline size_t group_topics_wave_bytes(int32_t Kp) { return 4 * (size_t)Kp * (sizeof(uint32_t) + sizeof(uint16_t)); }
+struct GroupTopicsArgs {
+  const int32_t* z;
+  const int64_t* doc_off;
+  const int32_t* doc_group;      // [D], -1 = left out
+  int64_t D, min_tokens;
+  double min_prop;
+  int32_t min_count, K, Kp, G;
+  int64_t o_present, o_shares, cells;
+  unsigned long long* buf;       // [cells]
+};
+hipError_t launch_group_topics(const GroupTopicsArgs& a, int blocks, int lds, hipStream_t st);
+// lda_subcorpus_* (DESIGN.md 9m): k_subcorpus_count adds 1 to sub[word, topic]
+// (V x Kp int32) for every token of the documents whose mask byte is nonzero,
+// one wave per document; k_subcorpus_add is dst += src over cells;
+// k_subcorpus_totals adds the column sums of sub to totals [K] (zero before).
+hipError_t launch_subcorpus_count(const int32_t* z, const int32_t* words, const int64_t* doc_off,
+                                  const uint8_t* mask, int64_t D, int32_t Kp, int32_t* sub, int blocks,
+                                  hipStream_t st);
+hipError_t launch_subcorpus_add(int32_t* dst, const int32_t* src, int64_t cells, hipStream_t st);
+hipError_t launch_subcorpus_totals(const int32_t* sub, int32_t V, int32_t K, int32_t Kp, long long* totals,
+                                   hipStream_t st);
 
 }  // namespace lda

@@ -6376,4 +6376,177 @@ hipError_t launch_topic_cooc(const TopicCoocArgs& a, int blocks, int lds, hipStr
   return hipSuccess;
 }
 
+// lda_group_topics: one wave per used document (group >= 0, L_d >= min_tokens),
+// grid-capped as k_topic_cooc.  A wave whose document is left out or too short
+// goes on at once (a left-out one after the single load of its group id).
+// Otherwise steps 1, 2 and 5 of k_topic_cooc -- the per-wave LDS histogram
+// [Kp] (uint32), the 16-bit list of the document's distinct topics built in
+// O(tokens) by the first-lane trick, clearing through the list -- and between
+// them lane e adds entry e's count to tokens[g, k], 1 to present[g, k] when the
+// topic is present, and floor(n_dk 2^32 / L_d) (one unsigned 64-bit division)
+// to shares[g, k]; lane 0 adds 1 to group_docs[g] and L_d to group_tokens[g].
+// buf is group_docs [G], group_tokens [G], tokens [G K], then present [G K]
+// and shares [G K] when requested (o_present / o_shares: their first cell, -1
+// when not requested).  LDS != 0: the block keeps a copy of buf's layout in
+// 64-bit LDS cells behind the four histograms and lists and adds its nonzero
+// cells to global memory once.  Otherwise every add is a global 64-bit atomic.
+// Integer adds only: the result is a function of z, whatever the grid and the
+// order.
+template <bool LDS>
+__global__ __launch_bounds__(256) void k_group_topics(const GroupTopicsArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int32_t h[];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int K = a.K, G = a.G;
+  uint32_t* hist = reinterpret_cast<uint32_t*>(h) + wid * a.Kp;
+  uint16_t* list = reinterpret_cast<uint16_t*>(h + 4 * a.Kp) + wid * a.Kp;
+  unsigned long long* blk = reinterpret_cast<unsigned long long*>(h + 6 * a.Kp);
+  const int64_t o_tok = 2 * (int64_t)G;
+  auto add = [&](int64_t cell, unsigned long long v) {
+    if (LDS)
+      atomicAdd(&blk[cell], v);
+    else
+      atomicAdd(&a.buf[cell], v);
+  };
+  for (int i = lane; i < a.Kp; i += 64) hist[i] = 0;
+  if (LDS)
+    for (int i = threadIdx.x; i < (int)a.cells; i += 256) blk[i] = 0;
+  __syncthreads();
+  const int32_t* __restrict__ z = a.z;
+  for (int64_t d = (int64_t)blockIdx.x * 4 + wid; d < a.D; d += (int64_t)gridDim.x * 4) {
+    const int g = a.doc_group[d];
+    if (g < 0) continue;
+    const int64_t t0 = a.doc_off[d], t1 = a.doc_off[d + 1], L = t1 - t0;
+    if (L < a.min_tokens) continue;
+    for (int64_t i = t0 + lane; i < t1; i += 64) atomicAdd(&hist[z[i]], 1u);
+    wave_lds_fence();
+    int m = 0;
+    for (int64_t b = t0; b < t1; b += 64) {
+      const int64_t i = b + lane;
+      int k = 0;
+      bool own = false;
+      if (i < t1) {
+        k = z[i];
+        own = (atomicOr(&hist[k], 0x80000000u) >> 31) == 0;
+      }
+      const uint64_t owners = __ballot(own);
+      if (own) list[m + __popcll(owners & ((1ull << lane) - 1))] = (uint16_t)k;
+      m += __popcll(owners);
+    }
+    wave_lds_fence();
+    const double thr = a.min_prop * (double)L;
+    if (lane == 0) {
+      add(g, 1ull);
+      add(G + g, (unsigned long long)L);
+    }
+    for (int e = lane; e < m; e += 64) {
+      const int k = list[e];
+      const int32_t c = (int32_t)(hist[k] & 0x7FFFFFFFu);
+      const int64_t cell = (int64_t)g * K + k;
+      add(o_tok + cell, (unsigned long long)c);
+      if (a.o_present >= 0 && c >= a.min_count && (double)c >= thr) add(a.o_present + cell, 1ull);
+      if (a.o_shares >= 0) add(a.o_shares + cell, ((unsigned long long)c << 32) / (unsigned long long)L);
+    }
+    wave_lds_fence();
+    for (int e = lane; e < m; e += 64) hist[list[e]] = 0;
+    wave_lds_fence();
+  }
+  if (!LDS) return;
+  __syncthreads();
+  for (int i = threadIdx.x; i < (int)a.cells; i += 256) {
+    const unsigned long long v = blk[i];
+    if (v) atomicAdd(&a.buf[i], v);
+  }
+}
+
+hipError_t launch_group_topics(const GroupTopicsArgs& a, int blocks, int lds, hipStream_t st) {
+  const int64_t gk = (int64_t)a.G * a.K;
+  const int ntab = 1 + (a.o_present >= 0) + (a.o_shares >= 0);
+  if (a.K < 1 || a.K > a.Kp || a.Kp > 4096 || (a.Kp & 63) != 0 || a.G < 1 || blocks < 1 || a.min_tokens < 1 ||
+      a.min_count < 1 || !a.buf || !a.doc_group || a.cells != 2 * (int64_t)a.G + ntab * gk ||
+      (a.o_present >= 0 && a.o_present != 2 * (int64_t)a.G + gk) ||
+      (a.o_shares >= 0 && a.o_shares != 2 * (int64_t)a.G + (ntab - 1) * gk))
+    return hipErrorInvalidValue;
+  if (a.D <= 0) return hipSuccess;
+  // four histograms and four 16-bit lists: 96 KiB at Kp = 4096
+  size_t bytes = group_topics_wave_bytes(a.Kp);
+  if (lds) {
+    bytes += (size_t)a.cells * sizeof(unsigned long long);
+    if (bytes > GROUP_TOPICS_LDS_BYTES) return hipErrorInvalidValue;
+  }
+  const void* fn = lds ? reinterpret_cast<const void*>(&k_group_topics<true>)
+                       : reinterpret_cast<const void*>(&k_group_topics<false>);
+  if (bytes > 65536) {   // Kp > 2730: past the default dynamic LDS limit
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return e;
+  }
+  if (lds)
+    hipLaunchKernelGGL(k_group_topics<true>, dim3(blocks), dim3(256), bytes, st, a);
+  else
+    hipLaunchKernelGGL(k_group_topics<false>, dim3(blocks), dim3(256), bytes, st, a);
+  return hipGetLastError();
+}
+
+// lda_subcorpus_count: one wave per document, grid-capped.  A masked-out
+// document costs the one load of its mask byte; the lanes of a masked-in one
+// stride over its tokens and add 1 to sub[word, topic] (int32 atomics: a cell
+// is bounded by the global nw cell).
+__global__ __launch_bounds__(256) void k_subcorpus_count(const int32_t* __restrict__ z,
+                                                         const int32_t* __restrict__ words,
+                                                         const int64_t* __restrict__ doc_off,
+                                                         const uint8_t* __restrict__ mask, int64_t D, int32_t Kp,
+                                                         int32_t* __restrict__ sub) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  for (int64_t d = (int64_t)blockIdx.x * 4 + wid; d < D; d += (int64_t)gridDim.x * 4) {
+    if (!mask[d]) continue;
+    const int64_t t0 = doc_off[d], t1 = doc_off[d + 1];
+    for (int64_t i = t0 + lane; i < t1; i += 64) atomicAdd(&sub[(size_t)words[i] * Kp + z[i]], 1);
+  }
+}
+
+hipError_t launch_subcorpus_count(const int32_t* z, const int32_t* words, const int64_t* doc_off,
+                                  const uint8_t* mask, int64_t D, int32_t Kp, int32_t* sub, int blocks,
+                                  hipStream_t st) {
+  if (!z || !words || !doc_off || !mask || !sub || Kp < 64 || blocks < 1) return hipErrorInvalidValue;
+  if (D <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_subcorpus_count, dim3(blocks), dim3(256), 0, st, z, words, doc_off, mask, D, Kp, sub);
+  return hipGetLastError();
+}
+
+// lda_subcorpus_merge: dst[i] += src[i]
+__global__ __launch_bounds__(256) void k_subcorpus_add(int32_t* __restrict__ dst, const int32_t* __restrict__ src,
+                                                       int64_t cells) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < cells; i += (int64_t)gridDim.x * 256)
+    dst[i] += src[i];
+}
+
+hipError_t launch_subcorpus_add(int32_t* dst, const int32_t* src, int64_t cells, hipStream_t st) {
+  if (!dst || !src || cells < 0) return hipErrorInvalidValue;
+  if (cells == 0) return hipSuccess;
+  const int blocks = (int)std::min<int64_t>((cells + 255) / 256, 4096);
+  hipLaunchKernelGGL(k_subcorpus_add, dim3(blocks), dim3(256), 0, st, dst, src, cells);
+  return hipGetLastError();
+}
+
+// lda_subcorpus_top_words' totals: totals[k] += the sum of column k over the
+// block's rows (V rows of Kp int32, K columns read); totals must be zero before
+// the launch.  Thread t takes columns t, t + 256, ...; a row is read coalesced.
+__global__ __launch_bounds__(256) void k_subcorpus_totals(const int32_t* __restrict__ sub, int32_t V, int32_t K,
+                                                          int32_t Kp, int32_t rows, long long* __restrict__ totals) {
+  const int64_t r0 = (int64_t)blockIdx.x * rows, r1 = r0 + rows < V ? r0 + rows : V;
+  for (int k = threadIdx.x; k < K; k += 256) {
+    long long s = 0;
+    for (int64_t r = r0; r < r1; ++r) s += sub[r * Kp + k];
+    if (s) atomicAdd(reinterpret_cast<unsigned long long*>(&totals[k]), (unsigned long long)s);
+  }
+}
+
+hipError_t launch_subcorpus_totals(const int32_t* sub, int32_t V, int32_t K, int32_t Kp, long long* totals,
+                                   hipStream_t st) {
+  if (!sub || !totals || V < 0 || K < 1 || K > Kp) return hipErrorInvalidValue;
+  if (V == 0) return hipSuccess;
+  const int32_t rows = 64;
+  hipLaunchKernelGGL(k_subcorpus_totals, dim3((V + rows - 1) / rows), dim3(256), 0, st, sub, V, K, Kp, rows, totals);
+  return hipGetLastError();
+}
+
 }  // namespace lda

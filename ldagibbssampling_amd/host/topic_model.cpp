@@ -1531,6 +1531,188 @@ std::string ParallelTopicModel::topicCorrelationsText(int32_t measure, int32_t n
   return topicCorrelationsFormat(K_, n, ids.data(), values.data());
 }
 
+// ---- topics by document group -------------------------------
+namespace {
+void checkGroupKind(int32_t kind) {
+  if (kind < LDATM_GROUP_TOKENS || kind > LDATM_GROUP_LIFT) raise(LDA_ERR_INVALID_ARG, "unknown kind (LDATM_GROUP_*)");
+}
+// lda_group_topics' host-side argument checks, in its order, before any shard is built
+void checkGroups(const int32_t* doc_group, int64_t D, int32_t G) {
+  if (D > 0 && !doc_group) raise(LDA_ERR_INVALID_ARG, "null doc_group");
+  for (int64_t d = 0; d < D; ++d)
+    if (doc_group[d] < -1 || doc_group[d] >= G)
+      raise(LDA_ERR_INVALID_ARG, "doc_group[" + std::to_string(d) + "] = " + std::to_string(doc_group[d]) +
+                                     " is outside [-1, G)");
+}
+}  // namespace
+
+void groupPrevalenceFinish(int32_t kind, int32_t G, int32_t K, const int64_t* group_docs, const int64_t* group_tokens,
+                           const int64_t* tokens, const int64_t* present, const uint64_t* shares, double* out) {
+  checkGroupKind(kind);
+  if (G < 1) raise(LDA_ERR_INVALID_ARG, "G must be at least 1");
+  if (K < 1) raise(LDA_ERR_INVALID_ARG, "K must be at least 1");
+  if (!group_docs || !group_tokens || !tokens)
+    raise(LDA_ERR_INVALID_ARG, "null input (group_docs, group_tokens and tokens are required)");
+  if (kind == LDATM_GROUP_DOCUMENTS && !present)
+    raise(LDA_ERR_INVALID_ARG, "missing table for the kind: documents takes present");
+  if (kind == LDATM_GROUP_MEAN && !shares) raise(LDA_ERR_INVALID_ARG, "missing table for the kind: mean takes shares");
+  if (!out) raise(LDA_ERR_INVALID_ARG, "null output");
+  const double nan = std::numeric_limits<double>::quiet_NaN(), inf = std::numeric_limits<double>::infinity();
+  const size_t Gs = (size_t)G, Ks = (size_t)K;
+  // lift's corpus side: N_k and N over the groups
+  std::vector<int64_t> nk(Ks, 0);
+  int64_t n_all = 0;
+  if (kind == LDATM_GROUP_LIFT)
+    for (size_t g = 0; g < Gs; ++g) {
+      n_all += group_tokens[g];
+      for (size_t k = 0; k < Ks; ++k) nk[k] += tokens[g * Ks + k];
+    }
+  for (size_t g = 0; g < Gs; ++g)
+    for (size_t k = 0; k < Ks; ++k) {
+      const size_t at = g * Ks + k;
+      double v = nan;
+      switch (kind) {
+        case LDATM_GROUP_TOKENS:
+          if (group_tokens[g] != 0) v = (double)tokens[at] / (double)group_tokens[g];
+          break;
+        case LDATM_GROUP_DOCUMENTS:
+          if (group_docs[g] != 0) v = (double)present[at] / (double)group_docs[g];
+          break;
+        case LDATM_GROUP_MEAN:
+          if (group_docs[g] != 0) v = (double)shares[at] / (4294967296.0 * (double)group_docs[g]);
+          break;
+        default:   // LDATM_GROUP_LIFT
+          if (group_tokens[g] == 0 || nk[k] == 0 || n_all == 0) break;
+          v = tokens[at] == 0 ? -inf
+                              : std::log(((double)tokens[at] / (double)group_tokens[g]) /
+                                         ((double)nk[k] / (double)n_all));
+          break;
+      }
+      out[at] = v;
+    }
+}
+
+void groupTopTopicsSelect(int32_t G, int32_t K, int32_t n, const double* matrix, int32_t* ids, double* values) {
+  if (G < 1) raise(LDA_ERR_INVALID_ARG, "G must be at least 1");
+  if (K < 1) raise(LDA_ERR_INVALID_ARG, "K must be at least 1");
+  if (n < 1) raise(LDA_ERR_INVALID_ARG, "n must be at least 1");
+  if (!matrix) raise(LDA_ERR_INVALID_ARG, "null matrix");
+  if (!ids || !values) raise(LDA_ERR_INVALID_ARG, "null output");
+  std::vector<int32_t> cand;
+  for (int32_t g = 0; g < G; ++g) {
+    const double* row = matrix + (size_t)g * (size_t)K;
+    cand.clear();
+    for (int32_t k = 0; k < K; ++k)
+      if (std::isfinite(row[k])) cand.push_back(k);
+    const size_t keep = std::min<size_t>((size_t)n, cand.size());
+    std::partial_sort(cand.begin(), cand.begin() + (std::ptrdiff_t)keep, cand.end(),
+                      [&](int32_t a, int32_t b) { return row[a] > row[b] || (row[a] == row[b] && a < b); });
+    for (int32_t i = 0; i < n; ++i) {
+      const bool has = (size_t)i < keep;
+      ids[(size_t)g * n + i] = has ? cand[(size_t)i] : -1;
+      values[(size_t)g * n + i] = has ? row[cand[(size_t)i]] : std::numeric_limits<double>::quiet_NaN();
+    }
+  }
+}
+
+std::string groupTopicsFormat(int32_t G, int32_t n, const int32_t* ids, const double* values) {
+  std::string out = "#group topic value\n";
+  for (int32_t g = 0; g < G; ++g)
+    for (int32_t i = 0; i < n; ++i) {
+      const size_t at = (size_t)g * n + i;
+      if (ids[at] < 0) break;
+      out += std::to_string(g) + " " + std::to_string(ids[at]) + " " + java_double(values[at]) + "\n";
+    }
+  return out;
+}
+
+void ParallelTopicModel::groupTopics(const int32_t* doc_group, int32_t G, int64_t min_tokens, int32_t min_count,
+                                     double min_prop, int64_t* group_docs, int64_t* group_tokens, int64_t* tokens,
+                                     int64_t* present, uint64_t* shares) {
+  if (G < 1) raise(LDA_ERR_INVALID_ARG, "G must be at least 1");
+  if (!group_docs || !group_tokens || !tokens)
+    raise(LDA_ERR_INVALID_ARG, "null output (group_docs, group_tokens and tokens are required)");
+  checkCooccurrence(min_tokens, min_count, min_prop);
+  checkGroups(doc_group, numDocs(), G);
+  if ((int64_t)G * K_ > LDA_GROUP_TOPICS_MAX_CELLS)
+    raise(LDA_ERR_UNSUPPORTED, "group topics: G x K above LDA_GROUP_TOPICS_MAX_CELLS");
+  ensureShards();
+  const size_t S = shards_->ctx.size(), Gs = (size_t)G, cells = Gs * (size_t)K_;
+  auto slice = [&](size_t s) { return doc_group ? doc_group + shards_->doc_begin[s] : nullptr; };
+  check(lda_group_topics(shards_->ctx[0], slice(0), G, min_tokens, min_count, min_prop, group_docs, group_tokens,
+                         tokens, present, shares),
+        "lda_group_topics");
+  if (S == 1) return;
+  // the other shards one at a time into buffers of one shard's size
+  std::vector<int64_t> gd(Gs), gt(Gs), tok(cells), pre(present ? cells : 0);
+  std::vector<uint64_t> shr(shares ? cells : 0);
+  for (size_t s = 1; s < S; ++s) {
+    check(lda_group_topics(shards_->ctx[s], slice(s), G, min_tokens, min_count, min_prop, gd.data(), gt.data(),
+                           tok.data(), present ? pre.data() : nullptr, shares ? shr.data() : nullptr),
+          "lda_group_topics");
+    for (size_t g = 0; g < Gs; ++g) {
+      group_docs[g] += gd[g];
+      group_tokens[g] += gt[g];
+    }
+    for (size_t i = 0; i < cells; ++i) tokens[i] += tok[i];
+    if (present)
+      for (size_t i = 0; i < cells; ++i) present[i] += pre[i];
+    if (shares)
+      for (size_t i = 0; i < cells; ++i) shares[i] += shr[i];
+  }
+}
+
+void ParallelTopicModel::groupPrevalence(const int32_t* doc_group, int32_t G, int32_t kind, int64_t min_tokens,
+                                         int32_t min_count, double min_prop, double* out) {
+  checkGroupKind(kind);
+  if (G < 1) raise(LDA_ERR_INVALID_ARG, "G must be at least 1");
+  checkCooccurrence(min_tokens, min_count, min_prop);
+  if (!out) raise(LDA_ERR_INVALID_ARG, "null output");
+  const size_t Gs = (size_t)G, cells = Gs * (size_t)K_;
+  std::vector<int64_t> gd(Gs), gt(Gs), tok(cells), pre(kind == LDATM_GROUP_DOCUMENTS ? cells : 0);
+  std::vector<uint64_t> shr(kind == LDATM_GROUP_MEAN ? cells : 0);
+  groupTopics(doc_group, G, min_tokens, min_count, min_prop, gd.data(), gt.data(), tok.data(),
+              pre.empty() ? nullptr : pre.data(), shr.empty() ? nullptr : shr.data());
+  groupPrevalenceFinish(kind, G, K_, gd.data(), gt.data(), tok.data(), pre.empty() ? nullptr : pre.data(),
+                        shr.empty() ? nullptr : shr.data(), out);
+}
+
+std::string ParallelTopicModel::groupTopicsText(const int32_t* doc_group, int32_t G, int32_t kind, int32_t n,
+                                                int64_t min_tokens, int32_t min_count, double min_prop) {
+  checkGroupKind(kind);
+  if (G < 1) raise(LDA_ERR_INVALID_ARG, "G must be at least 1");
+  if (n < 1) raise(LDA_ERR_INVALID_ARG, "n must be at least 1");
+  checkCooccurrence(min_tokens, min_count, min_prop);
+  std::vector<double> matrix((size_t)G * (size_t)K_);
+  groupPrevalence(doc_group, G, kind, min_tokens, min_count, min_prop, matrix.data());
+  std::vector<int32_t> ids((size_t)G * (size_t)n);
+  std::vector<double> values((size_t)G * (size_t)n);
+  groupTopTopicsSelect(G, K_, n, matrix.data(), ids.data(), values.data());
+  return groupTopicsFormat(G, n, ids.data(), values.data());
+}
+
+void ParallelTopicModel::subCorpusTopWords(const uint8_t* doc_mask, int32_t n, int32_t* word_ids, int32_t* counts,
+                                           int64_t* totals) {
+  if (n < 1 || n > LDA_TOP_WORDS_MAX) raise(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_TOP_WORDS_MAX]");
+  if (!word_ids || !counts || !totals) raise(LDA_ERR_INVALID_ARG, "null output");
+  if (numDocs() > 0 && !doc_mask) raise(LDA_ERR_INVALID_ARG, "null doc_mask");
+  ensureShards();
+  // the tables live for this call only, whatever its end
+  struct Release {
+    std::vector<lda_ctx*>& ctx;
+    ~Release() {
+      for (auto c : ctx) (void)lda_subcorpus_release(c);
+    }
+  } release{shards_->ctx};
+  const size_t S = shards_->ctx.size();
+  for (size_t s = 0; s < S; ++s)
+    check(lda_subcorpus_count(shards_->ctx[s], doc_mask ? doc_mask + shards_->doc_begin[s] : nullptr, 0),
+          "lda_subcorpus_count");
+  // the top n of a sum is not a merge of the shards' top n: add the tables, then select
+  for (size_t s = 1; s < S; ++s) check(lda_subcorpus_merge(shards_->ctx[0], shards_->ctx[s]), "lda_subcorpus_merge");
+  check(lda_subcorpus_top_words(shards_->ctx[0], n, word_ids, counts, totals), "lda_subcorpus_top_words");
+}
+
 namespace {
 // Mallet's TopicModelDiagnostics thresholds (its DEFAULT_DOC_PROPORTIONS)
 constexpr double DIAG_PROPS[LDATM_DIAG_PROPS] = {0.01, 0.02, 0.05, 0.1, 0.2, 0.3, 0.5};
@@ -2874,6 +3056,71 @@ lda_status ldatm_topic_correlations_format(int32_t K, int32_t n, const int32_t* 
   std::string s;
   lda_status st = guard([&] { s = lda_host::topicCorrelationsFormat(K, n, ids, values); });
   return st ? st : copy_text(s, buf, cap, len);
+}
+
+lda_status ldatm_group_topics(ldatm* m, const int32_t* doc_group, int32_t G, int64_t min_tokens, int32_t min_count,
+                              double min_prop, int64_t* group_docs, int64_t* group_tokens, int64_t* tokens,
+                              int64_t* present, uint64_t* shares) {
+  TM_CHECK(m);
+  return guard([&] {
+    m->model.groupTopics(doc_group, G, min_tokens, min_count, min_prop, group_docs, group_tokens, tokens, present,
+                         shares);
+  });
+}
+
+lda_status ldatm_group_prevalence_finish(int32_t kind, int32_t G, int32_t K, const int64_t* group_docs,
+                                         const int64_t* group_tokens, const int64_t* tokens, const int64_t* present,
+                                         const uint64_t* shares, double* out) {
+  return guard([&] {
+    lda_host::groupPrevalenceFinish(kind, G, K, group_docs, group_tokens, tokens, present, shares, out);
+  });
+}
+
+lda_status ldatm_group_prevalence(ldatm* m, const int32_t* doc_group, int32_t G, int32_t kind, int64_t min_tokens,
+                                  int32_t min_count, double min_prop, double* out) {
+  TM_CHECK(m);
+  return guard([&] { m->model.groupPrevalence(doc_group, G, kind, min_tokens, min_count, min_prop, out); });
+}
+
+lda_status ldatm_group_top_topics_select(int32_t G, int32_t K, int32_t n, const double* matrix, int32_t* ids,
+                                         double* values) {
+  return guard([&] { lda_host::groupTopTopicsSelect(G, K, n, matrix, ids, values); });
+}
+
+lda_status ldatm_group_topics_text(ldatm* m, const int32_t* doc_group, int32_t G, int32_t kind, int32_t n,
+                                   int64_t min_tokens, int32_t min_count, double min_prop, char* buf, size_t cap,
+                                   size_t* len) {
+  TM_CHECK(m);
+  std::string s;
+  lda_status st =
+      guard([&] { s = m->model.groupTopicsText(doc_group, G, kind, n, min_tokens, min_count, min_prop); });
+  return st ? st : copy_text(s, buf, cap, len);
+}
+
+lda_status ldatm_print_group_topics(ldatm* m, const char* path, const int32_t* doc_group, int32_t G, int32_t kind,
+                                    int32_t n, int64_t min_tokens, int32_t min_count, double min_prop) {
+  TM_CHECK(m);
+  std::string s;
+  lda_status st =
+      guard([&] { s = m->model.groupTopicsText(doc_group, G, kind, n, min_tokens, min_count, min_prop); });
+  return st ? st : write_file(path, s);
+}
+
+lda_status ldatm_group_topics_format(int32_t G, int32_t n, const int32_t* ids, const double* values, char* buf,
+                                     size_t cap, size_t* len) {
+  if (G < 1 || n < 1 || !ids || !values) {
+    g_tm_error = "bad argument";
+    return LDA_ERR_INVALID_ARG;
+  }
+  std::string s;
+  lda_status st = guard([&] { s = lda_host::groupTopicsFormat(G, n, ids, values); });
+  return st ? st : copy_text(s, buf, cap, len);
+}
+
+lda_status ldatm_subcorpus_top_words(ldatm* m, const uint8_t* doc_mask, int32_t n, int32_t* word_ids, int32_t* counts,
+                                     int64_t* totals) {
+  TM_CHECK(m);
+  return guard([&] { m->model.subCorpusTopWords(doc_mask, n, word_ids, counts, totals); });
 }
 
 lda_status ldatm_save(ldatm* m, const char* path) {

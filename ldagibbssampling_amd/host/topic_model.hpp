@@ -79,6 +79,15 @@ void topicCorrelationFinish(int32_t measure, int32_t K, int64_t docs_used, const
 void topicPartnersSelect(int32_t K, int32_t n, const double* matrix, int32_t* ids, double* values);
 std::string topicCorrelationsFormat(int32_t K, int32_t n, const int32_t* ids, const double* values);
 
+// Topics by document group, host only: the G x K matrix of a
+// kind (LDATM_GROUP_*) from lda_group_topics' integers, each group's n largest
+// finite values of a G x K matrix (value descending, then smaller topic id,
+// -1 / NaN past the last), and that selection's text.
+void groupPrevalenceFinish(int32_t kind, int32_t G, int32_t K, const int64_t* group_docs, const int64_t* group_tokens,
+                           const int64_t* tokens, const int64_t* present, const uint64_t* shares, double* out);
+void groupTopTopicsSelect(int32_t G, int32_t K, int32_t n, const double* matrix, int32_t* ids, double* values);
+std::string groupTopicsFormat(int32_t G, int32_t n, const int32_t* ids, const double* values);
+
 class ParallelTopicModel {
  public:
   ParallelTopicModel(int32_t num_topics, double alpha_sum, double beta);
@@ -204,6 +213,20 @@ class ParallelTopicModel {
                      int32_t* ids, double* values);
   std::string topicCorrelationsText(int32_t measure, int32_t n, int64_t min_tokens, int32_t min_count,
                                     double min_prop);
+
+  // lda_group_topics on every shard with its slice of doc_group (global
+  // document ids), summed (integers: exact); the matrix of one kind, counting
+  // only the table it needs; each group's n largest topics by it as text; each
+  // topic's top words inside the masked documents (every shard counts its
+  // slice, the tables are added into shard 0's, which selects; the tables are
+  // released).  The arguments are checked before any shard is built.
+  void groupTopics(const int32_t* doc_group, int32_t G, int64_t min_tokens, int32_t min_count, double min_prop,
+                   int64_t* group_docs, int64_t* group_tokens, int64_t* tokens, int64_t* present, uint64_t* shares);
+  void groupPrevalence(const int32_t* doc_group, int32_t G, int32_t kind, int64_t min_tokens, int32_t min_count,
+                       double min_prop, double* out);
+  std::string groupTopicsText(const int32_t* doc_group, int32_t G, int32_t kind, int32_t n, int64_t min_tokens,
+                              int32_t min_count, double min_prop);
+  void subCorpusTopWords(const uint8_t* doc_mask, int32_t n, int32_t* word_ids, int32_t* counts, int64_t* totals);
 
   // ---- topic diagnostics --------------------------------
   // lda_topic_codocuments on every shard with the caller's lists, summed in

@@ -575,6 +575,66 @@ class GibbsSampler:
         out["docs_used"] = int(used.value)
         return out
 
+    def group_topics(self, doc_group, G=None, stats=capi.GROUP_TOPICS_STATS, min_tokens: int = 10,
+                     min_count: int = 2, min_prop: float = 0.05) -> dict:
+        """lda_group_topics: how much of each group of this shard's documents is
+        each topic, counted on the device from z.  doc_group holds one id in
+        [-1, G) per document (-1 leaves it out; G = None: the largest id plus
+        one).  A document is used with a group >= 0 and at least min_tokens
+        tokens; topic k is present in it with n_dk >= min_count and n_dk >=
+        min_prop * L_d.  Returns a dict: "group_docs" [G] and "group_tokens"
+        [G] (int64: the used documents and their tokens), "tokens" [G, K]
+        (int64: sum of n_dk) and, of "present" ([G, K] int64: documents with k
+        present) and "shares" ([G, K] uint64: sum of floor(n_dk 2^32 / L_d))
+        those named in stats; only they are counted."""
+        stats = capi.group_topics_stats(stats)
+        min_tokens, min_count, min_prop = capi.topic_cooc_thresholds(min_tokens, min_count, min_prop)
+        ids, G = capi.group_ids(doc_group, self.D, G)
+        out = {"group_docs": np.zeros(G, np.int64), "group_tokens": np.zeros(G, np.int64),
+               "tokens": np.zeros((G, self.K), np.int64)}
+        for s in stats:
+            out[s] = np.zeros((G, self.K), np.uint64 if s == "shares" else np.int64)
+        tabs = [out[s].ctypes.data if s in out else None for s in capi.GROUP_TOPICS_STATS]
+        capi.check(self._L.lda_group_topics(self._h, ids.ctypes.data, G, min_tokens, min_count, min_prop,
+                                            out["group_docs"].ctypes.data, out["group_tokens"].ctypes.data,
+                                            out["tokens"].ctypes.data, *tabs), "lda_group_topics")
+        return out
+
+    def subcorpus_count(self, mask, accumulate: bool = False):
+        """lda_subcorpus_count: the context's sub-corpus table sub[V, Kp]
+        becomes (accumulate: grows by) the (word, topic) counts of this shard's
+        documents whose mask entry is nonzero.  The table is a snapshot of z
+        now; sampling never touches it."""
+        m = capi.doc_mask(mask, self.D)
+        capi.check(self._L.lda_subcorpus_count(self._h, m.ctypes.data, 1 if accumulate else 0),
+                   "lda_subcorpus_count")
+
+    def subcorpus_merge(self, other: "GibbsSampler"):
+        """lda_subcorpus_merge: this context's table += other's (same V and K,
+        a table each); other's is unchanged."""
+        if not isinstance(other, GibbsSampler):
+            raise TypeError("other must be a GibbsSampler")
+        capi.check(self._L.lda_subcorpus_merge(self._h, other._h), "lda_subcorpus_merge")
+
+    def subcorpus_top_words(self, n: int):
+        """lda_subcorpus_top_words: top_words' selection on the sub-corpus
+        table.  Returns (word_ids[K, n], counts[K, n]) int32, -1 / 0 past a
+        topic's last nonzero word, and totals[K] int64, each topic's tokens in
+        the sub-corpus."""
+        n = int(n)
+        if not 1 <= n <= capi.TOP_WORDS_MAX:
+            raise ValueError(f"n must be in [1, {capi.TOP_WORDS_MAX}]")
+        ids = np.zeros((self.K, n), dtype=np.int32)
+        cnt = np.zeros((self.K, n), dtype=np.int32)
+        tot = np.zeros(self.K, dtype=np.int64)
+        capi.check(self._L.lda_subcorpus_top_words(self._h, n, ids.ctypes.data, cnt.ctypes.data, tot.ctypes.data),
+                   "lda_subcorpus_top_words")
+        return ids, cnt, tot
+
+    def subcorpus_release(self):
+        """lda_subcorpus_release: frees the sub-corpus table, if there is one."""
+        capi.check(self._L.lda_subcorpus_release(self._h), "lda_subcorpus_release")
+
     def _word_lists(self, word_ids):
         """(ids[K, n] int32, n) of K word lists, -1 = an empty slot."""
         ids = np.ascontiguousarray(word_ids, dtype=np.int32)

@@ -118,6 +118,15 @@ TM_SIGNATURES = {
                                              C.POINTER(C.c_size_t)]),
     "ldatm_print_topic_correlations": (_i32, [_vp, C.c_char_p, _i32, _i32, C.c_int64, _i32, C.c_double]),
     "ldatm_topic_correlations_format": (_i32, [_i32, _i32, _vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ldatm_group_topics": (_i32, [_vp, _vp, _i32, C.c_int64, _i32, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "ldatm_group_prevalence_finish": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ldatm_group_prevalence": (_i32, [_vp, _vp, _i32, _i32, C.c_int64, _i32, C.c_double, _vp]),
+    "ldatm_group_top_topics_select": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp]),
+    "ldatm_group_topics_text": (_i32, [_vp, _vp, _i32, _i32, _i32, C.c_int64, _i32, C.c_double, _vp, C.c_size_t,
+                                       C.POINTER(C.c_size_t)]),
+    "ldatm_print_group_topics": (_i32, [_vp, C.c_char_p, _vp, _i32, _i32, _i32, C.c_int64, _i32, C.c_double]),
+    "ldatm_group_topics_format": (_i32, [_i32, _i32, _vp, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ldatm_subcorpus_top_words": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp]),
     "ldatm_save": (_i32, [_vp, C.c_char_p]),
     "ldatm_load": (_i32, [C.POINTER(_vp), C.c_char_p]),
     "ldatm_infer": (_i32, [_vp, C.c_int64, _i64p, _vp, _i32, _i32, _i32, C.c_uint64, _f64p]),
@@ -405,6 +414,108 @@ def format_topic_correlations(ids, values) -> str:
     _check(L.ldatm_topic_correlations_format(*args, buf, size.value + 1, C.byref(size)),
            "ldatm_topic_correlations_format")
     return buf.value.decode()
+
+
+# LDATM_GROUP_* of lda_topic_model.h, and the optional table each kind takes
+GROUP_KINDS = {"tokens": 0, "documents": 1, "mean": 2, "lift": 3}
+GROUP_KIND_TABLE = {"tokens": None, "documents": "present", "mean": "shares", "lift": None}
+
+
+def group_kind(kind) -> str:
+    """A kind of group prevalence by name."""
+    if kind not in GROUP_KINDS:
+        raise ValueError(f"unknown kind {kind!r}: one of {tuple(GROUP_KINDS)}")
+    return kind
+
+
+def group_labels(groups) -> tuple:
+    """(labels, ids int32 [D]) of one label per document: the sorted distinct
+    labels that are not None, and per document its label's index, -1 for
+    None."""
+    groups = list(groups)
+    distinct = {g for g in groups if g is not None}
+    try:
+        labels = sorted(distinct)
+    except TypeError:                       # labels of several types: by type name, then text
+        labels = sorted(distinct, key=lambda g: (type(g).__name__, str(g)))
+    index = {g: i for i, g in enumerate(labels)}
+    ids = np.fromiter((-1 if g is None else index[g] for g in groups), dtype=np.int32, count=len(groups))
+    return labels, ids
+
+
+def group_prevalence_finish(kind, group_docs, group_tokens, tokens, present=None, shares=None) -> np.ndarray:
+    """ldatm_group_prevalence_finish (host only, no device): the float64
+    [G, K] matrix of a kind out of group_topics' integers -- "tokens" =
+    tokens / group_tokens, "documents" = present / group_docs, "mean" = shares /
+    (2^32 group_docs), "lift" = log((tokens / group_tokens) / (N_k / N)).  NaN
+    where a denominator is 0, lift -inf where tokens is 0.  A kind without its
+    table is an error."""
+    kind = group_kind(kind)
+    gd = np.ascontiguousarray(group_docs, np.int64)
+    gt = np.ascontiguousarray(group_tokens, np.int64)
+    tok = np.ascontiguousarray(tokens, np.int64)
+    if tok.ndim != 2 or tok.size == 0 or gd.shape != (tok.shape[0],) or gt.shape != (tok.shape[0],):
+        raise ValueError("group_docs and group_tokens must be [G] and tokens [G, K]")
+    pre = None if present is None else np.ascontiguousarray(present, np.int64)
+    shr = None if shares is None else np.ascontiguousarray(shares, np.uint64)
+    for t in (pre, shr):
+        if t is not None and t.shape != tok.shape:
+            raise ValueError("present and shares must be [G, K] as tokens")
+    G, K = tok.shape
+    out = np.zeros((G, K), np.float64)
+    _check(load_tm().ldatm_group_prevalence_finish(GROUP_KINDS[kind], G, K, gd.ctypes.data, gt.ctypes.data,
+                                                   tok.ctypes.data, None if pre is None else pre.ctypes.data,
+                                                   None if shr is None else shr.ctypes.data, out.ctypes.data),
+           "ldatm_group_prevalence_finish")
+    return out
+
+
+def group_top_topics_select(matrix, n: int):
+    """ldatm_group_top_topics_select (host only): per row g of a [G, K] matrix
+    the n columns with the largest finite values, larger first, equal values by
+    smaller id.  Returns (ids int32 [G, n], values float64 [G, n]), -1 / NaN
+    past the last."""
+    mat = np.ascontiguousarray(matrix, np.float64)
+    n = int(n)
+    if mat.ndim != 2 or mat.size == 0:
+        raise ValueError("matrix must be [G, K]")
+    if n < 1:
+        raise ValueError("n must be at least 1")
+    G, K = mat.shape
+    ids = np.zeros((G, n), np.int32)
+    values = np.zeros((G, n), np.float64)
+    _check(load_tm().ldatm_group_top_topics_select(G, K, n, mat.ctypes.data, ids.ctypes.data, values.ctypes.data),
+           "ldatm_group_top_topics_select")
+    return ids, values
+
+
+def format_group_topics(ids, values) -> str:
+    """ldatm_group_topics_format (host only): printGroupTopics' text from
+    [G, n] topic ids and values."""
+    ids = np.ascontiguousarray(ids, np.int32)
+    values = np.ascontiguousarray(values, np.float64)
+    if ids.ndim != 2 or values.shape != ids.shape or ids.size == 0:
+        raise ValueError("ids and values must be [G, n] arrays of one shape")
+    G, n = ids.shape
+    L = load_tm()
+    size = C.c_size_t()
+    args = (G, n, ids.ctypes.data, values.ctypes.data)
+    _check(L.ldatm_group_topics_format(*args, None, 0, C.byref(size)), "ldatm_group_topics_format")
+    buf = C.create_string_buffer(size.value + 1)
+    _check(L.ldatm_group_topics_format(*args, buf, size.value + 1, C.byref(size)), "ldatm_group_topics_format")
+    return buf.value.decode()
+
+
+class TopicsByGroup:
+    """What ParallelTopicModel.topicsByGroup returns: labels (the groups, in
+    the order of the rows), values (float64 [G, K] of the kind), groupDocs and
+    groupTokens (int64 [G]: the used documents of each group and their tokens)
+    and counts (the integer tables: "tokens" and, where counted, "present" and
+    "shares", [G, K])."""
+
+    def __init__(self, kind, labels, values, groupDocs, groupTokens, counts):
+        self.kind, self.labels, self.values = kind, labels, values
+        self.groupDocs, self.groupTokens, self.counts = groupDocs, groupTokens, counts
 
 
 class Alphabet:
@@ -991,6 +1102,106 @@ class ParallelTopicModel:
             k, l = np.nonzero(np.triu(mat >= cutoff, 1))
         return [(int(a), int(b), float(mat[a, b])) for a, b in zip(k, l)]
 
+    # ------------------------------- topics by document group
+    def _groups(self, groups):
+        """(labels, ids int32 [D]) of one label per document; None takes each
+        instance's target.  A document whose label is None is left out."""
+        if groups is None:
+            groups = [i.target for i in self.data]
+        labels, ids = group_labels(groups)
+        if len(ids) != len(self.data):
+            raise ValueError(f"groups must hold one label per document ({len(self.data)})")
+        if not labels:
+            raise ValueError("no groups: every label is None")
+        return labels, ids
+
+    def groupTopics(self, doc_group, G=None, stats=capi.GROUP_TOPICS_STATS, minTokens: int = 10, minCount: int = 2,
+                    minProp: float = 0.05) -> dict:
+        """ldatm_group_topics: GibbsSampler.group_topics over the whole model,
+        summed over the shards; doc_group holds one id in [-1, G) per document
+        in the model's order."""
+        stats = capi.group_topics_stats(stats)
+        thr = capi.topic_cooc_thresholds(minTokens, minCount, minProp)
+        ids, G = capi.group_ids(doc_group, len(self.data), G)
+        K = self.numTopics
+        out = {"group_docs": np.zeros(G, np.int64), "group_tokens": np.zeros(G, np.int64),
+               "tokens": np.zeros((G, K), np.int64)}
+        for s in stats:
+            out[s] = np.zeros((G, K), np.uint64 if s == "shares" else np.int64)
+        tabs = [out[s].ctypes.data if s in out else None for s in capi.GROUP_TOPICS_STATS]
+        _check(self._L.ldatm_group_topics(self._h, ids.ctypes.data, G, *thr, out["group_docs"].ctypes.data,
+                                          out["group_tokens"].ctypes.data, out["tokens"].ctypes.data, *tabs),
+               "groupTopics")
+        return out
+
+    def topicsByGroup(self, groups=None, kind="mean", stats=None, minTokens: int = 10, minCount: int = 2,
+                      minProp: float = 0.05) -> TopicsByGroup:
+        """How much of each group of documents is each topic.  groups holds
+        one label per document (None leaves a document out); groups = None
+        takes each instance's target.  The sorted distinct labels are the rows.
+        kind: "mean" (the mean over the group's documents of the topic's
+        proportion, what jsLDA plots over time), "tokens" (the topic's share
+        of the group's tokens), "documents" (the share of the group's documents
+        in which the topic is present), "lift" (log of the token share over the
+        topic's share of all groups).  A document counts with at least
+        minTokens tokens; a topic is present with n_dk >= minCount and n_dk >=
+        minProp * L_d.  Counted on the GPU from z; stats names further integer
+        tables to count beside the kind's own."""
+        kind = group_kind(kind)
+        need = GROUP_KIND_TABLE[kind]
+        stats = capi.group_topics_stats(() if stats is None else stats)
+        if need is not None and need not in stats:
+            stats = capi.group_topics_stats(stats + (need,))
+        labels, ids = self._groups(groups)
+        c = self.groupTopics(ids, len(labels), stats, minTokens, minCount, minProp)
+        values = group_prevalence_finish(kind, c["group_docs"], c["group_tokens"], c["tokens"], c.get("present"),
+                                         c.get("shares"))
+        return TopicsByGroup(kind, labels, values, c.pop("group_docs"), c.pop("group_tokens"), c)
+
+    def getGroupTopTopics(self, n: int = 5, groups=None, kind="mean", minTokens: int = 10, minCount: int = 2,
+                          minProp: float = 0.05) -> dict:
+        """Per label a list of (topic, value), at most n long, largest first
+        (equal values by smaller topic, non-finite values left out)."""
+        n = int(n)
+        if n < 1:
+            raise ValueError("n must be at least 1")
+        r = self.topicsByGroup(groups, kind, None, minTokens, minCount, minProp)
+        ids, values = group_top_topics_select(r.values, n)
+        return {label: [(int(t), float(v)) for t, v in zip(ids[g], values[g]) if t >= 0]
+                for g, label in enumerate(r.labels)}
+
+    def subCorpusTopWords(self, mask, n: int):
+        """ldatm_subcorpus_top_words: (word_ids[K, n], counts[K, n]) int32 and
+        totals[K] int64 -- topWords' selection inside the documents whose mask
+        entry is nonzero, counted on the GPU from z and added over the shards
+        before selecting."""
+        n = int(n)
+        if not 1 <= n <= capi.TOP_WORDS_MAX:
+            raise ValueError(f"n must be in [1, {capi.TOP_WORDS_MAX}]")
+        m = capi.doc_mask(mask, len(self.data))
+        ids = np.zeros((self.numTopics, n), np.int32)
+        cnt = np.zeros((self.numTopics, n), np.int32)
+        tot = np.zeros(self.numTopics, np.int64)
+        _check(self._L.ldatm_subcorpus_top_words(self._h, m.ctypes.data if len(m) else None, n, ids.ctypes.data,
+                                                 cnt.ctypes.data, tot.ctypes.data), "subCorpusTopWords")
+        return ids, cnt, tot
+
+    def getSubCorpusTopWords(self, mask, n: int) -> list:
+        """Per topic a list of (word, count), at most n long, heaviest first,
+        inside the documents whose mask entry is nonzero."""
+        ids, cnt, _ = self.subCorpusTopWords(mask, n)
+        name = (lambda w: w) if self.alphabet is None else self.alphabet.lookupObject
+        return [[(name(int(w)), int(c)) for w, c in zip(ids[k], cnt[k]) if w >= 0]
+                for k in range(self.numTopics)]
+
+    def getGroupTopWords(self, label, n: int, groups=None) -> list:
+        """getSubCorpusTopWords over the documents whose label (groups, or the
+        instances' targets) equals label."""
+        labels, ids = self._groups(groups)
+        if label not in labels:
+            raise ValueError(f"unknown label {label!r}")
+        return self.getSubCorpusTopWords(ids == labels.index(label), n)
+
     # ------------------------------- topic distances (DESIGN 9g)
     def _other_model(self, other):
         """(native handle or None, K2) of the other side of a topic
@@ -1253,6 +1464,30 @@ class ParallelTopicModel:
         thr = capi.topic_cooc_thresholds(minTokens, minCount, minProp)
         _check(self._L.ldatm_print_topic_correlations(self._h, os.fsencode(path), m, n, *thr),
                "printTopicCorrelations")
+
+    def groupTopicsText(self, n: int = 5, kind="mean", groups=None, minTokens: int = 10, minCount: int = 2,
+                        minProp: float = 0.05) -> str:
+        """printGroupTopics' text: "#group topic value", then per group and
+        rank "group topic value"; a group is the index of its label among the
+        sorted distinct labels (topicsByGroup(...).labels)."""
+        n = int(n)
+        if n < 1:
+            raise ValueError("n must be at least 1")
+        k = GROUP_KINDS[group_kind(kind)]
+        thr = capi.topic_cooc_thresholds(minTokens, minCount, minProp)
+        labels, ids = self._groups(groups)
+        return self._text(self._L.ldatm_group_topics_text, ids.ctypes.data, len(labels), k, n, *thr)
+
+    def printGroupTopics(self, path, n: int = 5, kind="mean", groups=None, minTokens: int = 10, minCount: int = 2,
+                         minProp: float = 0.05):
+        n = int(n)
+        if n < 1:
+            raise ValueError("n must be at least 1")
+        k = GROUP_KINDS[group_kind(kind)]
+        thr = capi.topic_cooc_thresholds(minTokens, minCount, minProp)
+        labels, ids = self._groups(groups)
+        _check(self._L.ldatm_print_group_topics(self._h, os.fsencode(path), ids.ctypes.data, len(labels), k, n, *thr),
+               "printGroupTopics")
 
     # ------------------------------------------------ checkpoint / resume
     def save(self, path):
