@@ -1076,6 +1076,89 @@ lda_status lda_topic_nearest(lda_ctx* ctx, lda_ctx* other /* NULL = ctx itself *
  * matrix (slab s holds rows [s * slab_rows, min(V, (s + 1) * slab_rows))). */
 lda_status lda_topic_distance_slabs(int32_t V, int32_t K, int32_t K2, int32_t* slabs, int32_t* slab_rows);
 
+/* ---- nearest documents --------------------------------------
+ * Distances between topic distributions of documents, and per query the n
+ * nearest documents of the shard, selected on the device: the document-side
+ * sibling of lda_topic_distances / lda_topic_nearest, and lda_score_docs'
+ * generalisation to more metrics.
+ *
+ * Candidate row.  Document d of ctx has the row
+ *     p_d[k] = ((double) n_dk + alpha_k) / ((double) L_d + A),
+ * n_dk from the shard's current z on the device, L_d its tokens, A = alpha[0]
+ * + ... + alpha[K-1] added in that order (lda_doc_top_topics' A).
+ * Query row.  Exactly one of theta / counts is given.
+ *   theta:  fp64 rows [Q * K], checked as lda_score_docs checks them (finite,
+ *           not negative, positive sum) and used as given; Hellinger and
+ *           Jensen-Shannon are then the stated expressions of that row
+ *           (distances when it sums to 1).
+ *   counts: int32 rows c [Q * K], not negative, turned on the device into
+ *           ((double) c_k + alpha_k) / ((double) sum c + A) with ctx's alpha:
+ *           the candidate's expression, so a query with the counts of a
+ *           candidate document is bit-identical to that candidate's row.
+ * Metrics (the LDA_TOPIC_* numbers 0..2; Kullback-Leibler is not offered).
+ * Everything is fp64, every sum over k runs in ascending k from 0.0, natural
+ * logarithms, x ln x = 0 at x = 0, no fused multiply-add (-ffp-contract=off),
+ * no floating-point atomics:
+ *   cosine (0)          S = sum p q, P2 = sum p^2, Q2 = sum q^2
+ *                       S / sqrt(P2 * Q2)                    larger is nearer
+ *   Hellinger (1)       S = sum (sqrt p - sqrt q)^2
+ *                       sqrt(min(1, S / 2))                  smaller is nearer
+ *   Jensen-Shannon (2)  S = sum (p + q) ln((p + q) / 2), Hp = sum p ln p,
+ *                       Hq = sum q ln q
+ *                       max(0, ((Hp + Hq) - S) / 2)          smaller is nearer
+ * Two bit-identical rows give exactly 0 (Hellinger, Jensen-Shannon) and
+ * exactly 1 (cosine).  Every reported value gets + 0.0: no -0.0 appears.
+ * Determinism.  A pair's value is a function of the two rows, K and the
+ * metric alone: not of where the pair sits in a tile, of the chunks, of M or
+ * Q, of the list order, of the shard's other documents or of the number of
+ * shards.  A call repeats bit for bit.
+ * Selection order.  Candidates are ordered by (value by the metric's order,
+ * document id ascending); the fp64 bit pattern is made monotone as
+ * lda_topic_nearest makes it.  Slots past the last candidate hold id -1 and
+ * value NaN.
+ *
+ * lda_doc_distances: out[q * M + j] = the value between query q and document
+ * docs[j] (or doc_begin + j), the documents addressed as lda_score_docs
+ * addresses them (a range, or a list in any order, duplicates allowed, with
+ * doc_begin = 0).
+ * lda_doc_nearest: per query the n nearest of all the shard's documents with
+ * L_d >= min_tokens, leaving out document skip[q] (-1: none; skip NULL: none):
+ * doc_ids[q * n + i] (shard-local), values[q * n + i].  Only the Q n ids and
+ * values come back.
+ * lda_doc_neighbors: the queries are the shard's own documents docs[j] (or
+ * doc_begin + j), their rows built on the device from z, each query's own id
+ * left out.  Bit-identical to lda_doc_counts followed by
+ * lda_doc_nearest(counts, skip = own id).
+ * Errors, checked in this order before any device work: LDA_ERR_INVALID_ARG
+ * for a NULL ctx ("null ctx"), a metric outside [0, 2] ("metric"), n outside
+ * [1, LDA_DOC_NEAREST_MAX] ("n"), both or neither of theta / counts
+ * ("theta / counts"), a NULL output with work to do ("null output"), Q < 0 or
+ * M < 0 ("bad sizes"), a document id or range outside [0, D) ("document"),
+ * min_tokens < 1 ("min_tokens"), a skip id outside [-1, D) ("skip"), a bad
+ * theta row ("theta"), a negative count ("counts"); LDA_ERR_STATE with a
+ * pending delta.  Q = 0 or M = 0 succeeds and touches nothing.
+ * Cost: Q D K pair terms, dense on purpose (with alpha > 0 no p is zero).
+ * Device scratch is grow-only, kept by ctx and bounded whatever Q and D are:
+ * the work goes in chunks of at most 1024 queries by at most
+ * min(2^23 / queries, 2^22 / K) candidates, so at most 64 MiB of chunk values,
+ * 32 MiB of candidate rows, 32 MiB of query rows (each padded to a multiple
+ * of 64 columns: at most 2 MiB more), 32 MiB of a query chunk's uploaded rows,
+ * and under 2 MiB of sums, lengths, ids and lists.  Waits for ctx's stream. */
+#define LDA_DOC_NEAREST_MAX 64
+lda_status lda_doc_distances(lda_ctx* ctx, int32_t metric, int64_t Q, const double* theta /* [Q*K] or NULL */,
+                             const int32_t* counts /* [Q*K] or NULL */, int64_t doc_begin, int64_t M,
+                             const int64_t* docs /* [M] or NULL */, double* out /* [Q*M] */);
+lda_status lda_doc_nearest(lda_ctx* ctx, int32_t metric, int32_t n, int64_t Q, const double* theta,
+                           const int32_t* counts, const int64_t* skip /* [Q] or NULL */, int32_t min_tokens,
+                           int64_t* doc_ids /* [Q*n] */, double* values /* [Q*n] */);
+lda_status lda_doc_neighbors(lda_ctx* ctx, int32_t metric, int32_t n, int64_t doc_begin, int64_t M,
+                             const int64_t* docs /* [M] or NULL */, int32_t min_tokens, int64_t* doc_ids /* [M*n] */,
+                             double* values /* [M*n] */);
+/* Test hook: at most `docs` candidates and `queries` queries per chunk (0 =
+ * the default of each), so that small tests run the second trip of every
+ * chunk loop and the merge of the running lists. */
+void lda_debug_doc_nearest_chunk(int64_t docs, int64_t queries);
+
 /* Mallet-layout adapter: typeTopicCounts as packed (count << topic_bits) |
  * topic rows sorted descending, rows[row_off[w] .. row_off[w+1]) with
  * row_off[V+1]; row length = min(K, typeTotal[w]) exactly as Mallet allocates
@@ -1195,8 +1278,9 @@ void lda_debug_fail_host_alloc(int32_t nth);
  * lda_debug_topic_cooccurrence_global), then lda_group_topics (with
  * lda_group_topics_path and its test hook lda_debug_group_topics_global) and
  * lda_subcorpus_count, lda_subcorpus_merge, lda_subcorpus_top_words and
- * lda_subcorpus_release came later and only add symbols, so the
- * version stays 8. */
+ * lda_subcorpus_release, then lda_doc_distances, lda_doc_nearest and
+ * lda_doc_neighbors (with their test hook lda_debug_doc_nearest_chunk) came
+ * later and only add symbols, so the version stays 8. */
 #define LDA_ABI_VERSION 8
 const char* lda_version(void);
 int32_t lda_abi_version(void);

@@ -20,6 +20,10 @@
  *   getInferencer().getSampledDistribution(...)   -> ldatm_infer
  *   the predict loop's similarity to every
  *   training document (Predictor.predict)        -> ldatm_score / ldatm_score_theta / ldatm_score_top
+ *   the same question for cosine, Hellinger and
+ *   Jensen-Shannon with the nearest documents
+ *   selected on the device                       -> ldatm_document_distances / ldatm_nearest_documents /
+ *                                                   ldatm_document_neighbors / ldatm_print_document_neighbors
  *   held-out log likelihood / perplexity by
  *   document completion, and its trace
  *   during estimate()                            -> ldatm_evaluate / ldatm_heldout_loglik / ldatm_set_held_out
@@ -207,6 +211,55 @@ lda_status ldatm_doc_counts(ldatm* m, int64_t M, const int64_t* docs, int32_t* n
 lda_status ldatm_topic_distances(ldatm* m, ldatm* other /* NULL = m */, int32_t metric, double* out /*[K*K2]*/);
 lda_status ldatm_nearest_topics(ldatm* m, ldatm* other /* NULL = m */, int32_t metric, int32_t n,
                                 int32_t* topics /*[K*n]*/, double* values /*[K*n]*/);
+
+/* Nearest documents (lda_doc_distances / lda_doc_nearest / lda_doc_neighbors
+ * of lda_mi355x.h, DESIGN 9n: the rows, the metrics LDA_TOPIC_COSINE,
+ * _HELLINGER, _JS, the selection order and the determinism contract are
+ * stated there).  Document ids are GLOBAL; queries are theta[Q*K] or
+ * counts[Q*K], exactly one of them.
+ * ldatm_document_distances: out[Q*M] against docs[M] (NULL: every document,
+ * M = the number of documents), routed to the shards as ldatm_score_theta
+ * routes.
+ * ldatm_nearest_documents: per query the n nearest of all documents with at
+ * least min_tokens tokens, document skip[q] left out (-1 or skip NULL: none);
+ * doc_ids[Q*n], values[Q*n], -1 / NaN past the last candidate.  Every shard
+ * selects among its own documents and the host merges the shards' lists by
+ * (value, global id): the result does not depend on the number of shards, bit
+ * for bit.
+ * ldatm_document_neighbors: the queries are the model's own documents docs[M]
+ * (NULL: all, M = the number of documents), each left out of its own list;
+ * doc_ids[M*n], values[M*n].  Neither theta nor counts cross to the host with
+ * one shard; with several, the counts of a chunk of queries do.  The same
+ * bits either way.
+ * ldatm_print_document_neighbors / ldatm_document_neighbors_text: the
+ * neighbours of every document as text, "#doc neighbor name value\n", then
+ * "<doc> <neighbor> <source|null-source of the neighbour> <value>\n" per
+ * document and rank, Java Double.toString values; empty slots print nothing.
+ * ldatm_document_neighbors_format: that text from the caller's M x n arrays
+ * (host only; docs NULL: the query of row j is j; names as
+ * ldatm_topic_documents_format).
+ * Errors, checked in this order before any device work (a model without a
+ * GPU names its bad argument): LDA_ERR_INVALID_ARG for a NULL model, a metric
+ * outside [0, 2], n outside [1, LDA_DOC_NEAREST_MAX], both or neither of
+ * theta / counts, a NULL output with work to do, Q < 0 or M < 0, M not the
+ * number of documents without a list, a document id outside [0, D),
+ * min_tokens < 1, a skip id outside [-1, D), a bad theta row, a negative
+ * count. */
+lda_status ldatm_document_distances(ldatm* m, int32_t metric, int64_t Q, const double* theta /*[Q*K] or NULL*/,
+                                    const int32_t* counts /*[Q*K] or NULL*/, int64_t M, const int64_t* docs,
+                                    double* out /*[Q*M]*/);
+lda_status ldatm_nearest_documents(ldatm* m, int32_t metric, int32_t n, int64_t Q, const double* theta,
+                                   const int32_t* counts, const int64_t* skip /*[Q] or NULL*/, int32_t min_tokens,
+                                   int64_t* doc_ids /*[Q*n]*/, double* values /*[Q*n]*/);
+lda_status ldatm_document_neighbors(ldatm* m, int32_t metric, int32_t n, int64_t M, const int64_t* docs,
+                                    int32_t min_tokens, int64_t* doc_ids /*[M*n]*/, double* values /*[M*n]*/);
+lda_status ldatm_document_neighbors_text(ldatm* m, int32_t n, int32_t metric, int32_t min_tokens, char* buf,
+                                         size_t cap, size_t* len);
+lda_status ldatm_print_document_neighbors(ldatm* m, const char* path, int32_t n, int32_t metric,
+                                          int32_t min_tokens);
+lda_status ldatm_document_neighbors_format(int64_t M, int32_t n, const int64_t* docs, const int64_t* doc_ids,
+                                           const double* values, const char* const* names, int64_t num_names,
+                                           char* buf, size_t cap, size_t* len);
 
 /* Topic diagnostics: per topic the figures Mallet's
  * TopicModelDiagnostics reports (train-topics --diagnostics-file), from

@@ -124,6 +124,10 @@ LTR_MAX_DOC_TOKENS = 4096
 # LDA_TOPIC_* metrics and LDA_TOPIC_NEAREST_MAX of lda_mi355x.h
 TOPIC_METRICS = {"cosine": 0, "hellinger": 1, "jensen_shannon": 2, "kullback_leibler": 3}
 TOPIC_NEAREST_MAX = 64
+# the metrics of lda_doc_distances / lda_doc_nearest / lda_doc_neighbors (the
+# LDA_TOPIC_* numbers 0..2) and LDA_DOC_NEAREST_MAX of lda_mi355x.h
+DOC_METRICS = {"cosine": 0, "hellinger": 1, "jensen_shannon": 2}
+DOC_NEAREST_MAX = 64
 
 
 def relevance_batch(n: int) -> int:
@@ -166,6 +170,46 @@ def topic_nearest_n(n) -> int:
     if not 1 <= n <= TOPIC_NEAREST_MAX:
         raise ValueError(f"n must be in [1, {TOPIC_NEAREST_MAX}]")
     return n
+
+
+def doc_metric(metric) -> int:
+    """The metric of the document calls (doc_distances, nearest_docs,
+    doc_neighbors): a name of DOC_METRICS or its integer; an unknown one is
+    refused before any native call."""
+    if isinstance(metric, str):
+        if metric not in DOC_METRICS:
+            raise ValueError(f"metric must be one of {sorted(DOC_METRICS)}, not {metric!r}")
+        return DOC_METRICS[metric]
+    if isinstance(metric, (bool, float)) or int(metric) not in DOC_METRICS.values():
+        raise ValueError(f"metric must be one of {sorted(DOC_METRICS)} or 0..2, not {metric!r}")
+    return int(metric)
+
+
+def doc_nearest_n(n) -> int:
+    n = int(n)
+    if not 1 <= n <= DOC_NEAREST_MAX:
+        raise ValueError(f"n must be in [1, {DOC_NEAREST_MAX}]")
+    return n
+
+
+def doc_queries(theta, counts, K: int):
+    """(theta fp64 [Q, K] or None, counts int32 [Q, K] or None) of the query
+    rows of the document calls: exactly one must be given, and a wrong shape
+    is refused before any native call."""
+    if (theta is None) == (counts is None):
+        raise ValueError("exactly one of theta and counts must be given")
+    if theta is not None:
+        return as_theta(theta, K), None
+    c = np.asarray(counts)
+    if c.ndim == 1:
+        c = c[None, :]
+    if c.ndim != 2 or c.shape[1] != K:
+        raise ValueError(f"counts must have shape [Q, {K}], not {list(np.shape(counts))}")
+    if not np.issubdtype(c.dtype, np.integer):
+        raise ValueError("counts must be integers")
+    if c.size and (c.min() < 0 or c.max() > np.iinfo(np.int32).max):
+        raise ValueError("counts must be non-negative int32 values")
+    return None, np.ascontiguousarray(c, dtype=np.int32)
 
 
 def score_metric(metric) -> int:
@@ -305,6 +349,10 @@ SIGNATURES = {
     "lda_topic_nearest": (C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
     "lda_topic_distance_slabs": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                              C.POINTER(C.c_int32)]),
+    "lda_doc_distances": (C.c_int32, [_vp, C.c_int32, C.c_int64, _vp, _vp, C.c_int64, C.c_int64, _vp, _vp]),
+    "lda_doc_nearest": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp, C.c_int32, _vp, _vp]),
+    "lda_doc_neighbors": (C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _vp, C.c_int32, _vp, _vp]),
+    "lda_debug_doc_nearest_chunk": (None, [C.c_int64, C.c_int64]),
     "lda_to_mallet_packed": (C.c_int32, [_vp, _vp, _i64p, C.POINTER(C.c_int32)]),
     "lda_max_doc_length": (C.c_int32, [_vp, C.POINTER(C.c_int32)]),
     "lda_doc_topic_histograms": (C.c_int32, [_vp, C.c_int32, _i32p, _i32p]),

@@ -302,6 +302,15 @@ constexpr int64_t CODOC_BLOCKS_PER_CU = 2;
 constexpr int64_t TOPIC_SLAB_ROWS = 256;
 constexpr int64_t TOPIC_PART_BYTES = int64_t(256) << 20;
 static_assert(TOPIC_PART_BYTES == LDA_TOPIC_SCRATCH_CAP_MIB * (int64_t(1) << 20), "the header states the cap");
+// lda_doc_distances / lda_doc_nearest / lda_doc_neighbors: queries per chunk,
+// fp64 values per chunk (64 MiB) and fp64 row cells of a side (32 MiB): the
+// scratch bound stated in lda_mi355x.h
+constexpr int64_t DOC_NEAR_QUERIES = 1024;
+constexpr int64_t DOC_NEAR_CELLS = int64_t(1) << 23;
+constexpr int64_t DOC_NEAR_ROW_CELLS = int64_t(1) << 22;
+static_assert(LDA_DOC_NEAREST_MAX == lda::DOC_NEAREST_MAX, "the header states the kernels' limit");
+static_assert(DOC_NEAR_QUERIES * LDA_MAX_TOPICS <= DOC_NEAR_ROW_CELLS, "a query chunk's rows fit their bound");
+int64_t g_doc_near_docs = 0, g_doc_near_queries = 0;   // lda_debug_doc_nearest_chunk (0: the defaults)
 
 }  // namespace
 
@@ -400,6 +409,18 @@ struct lda_ctx {
   double *ro_part = nullptr, *ro_sums = nullptr, *ro_mat = nullptr, *ro_vals = nullptr;
   int32_t* ro_ids = nullptr;
   size_t ro_cap[8] = {};
+  // lda_doc_distances / lda_doc_nearest / lda_doc_neighbors: grow-only
+  // scratch -- the transposed rows and sums of a query chunk and a candidate
+  // chunk, the candidates' lengths, the chunk's values [Qc x Dc], a query
+  // chunk's uploaded rows, the chunks' document ids and skip ids, and the two
+  // running lists (ids, values: [Qc x n] each)
+  double *dn_qrows = nullptr, *dn_crows = nullptr, *dn_qsums = nullptr, *dn_csums = nullptr, *dn_vals = nullptr;
+  double* dn_lvals[2] = {};
+  int64_t* dn_lids[2] = {};
+  int64_t *dn_cdocs = nullptr, *dn_qdocs = nullptr, *dn_skip = nullptr;
+  int32_t* dn_lens = nullptr;
+  unsigned long long* dn_up = nullptr;
+  size_t dn_cap[14] = {};
   // lda_topic_codocuments / lda_topic_word_stats: grow-only scratch -- the
   // word lists [K n], the (word, topic) -> slot table, the integer results
   // and lda_topic_word_stats' fp64 sums
@@ -609,6 +630,9 @@ struct lda_ctx {
                     (void*)ltr_z, (void*)ltr_words, (void*)ltr_p, (void*)ltr_phat, (void*)ltr_ll, (void*)ltr_off,
                     (void*)ro_lists, (void*)ro_out, (void*)ro_docs,
                     (void*)ro_part, (void*)ro_sums, (void*)ro_mat, (void*)ro_vals, (void*)ro_ids,
+                    (void*)dn_qrows, (void*)dn_crows, (void*)dn_qsums, (void*)dn_csums, (void*)dn_vals,
+                    (void*)dn_lvals[0], (void*)dn_lvals[1], (void*)dn_lids[0], (void*)dn_lids[1], (void*)dn_cdocs,
+                    (void*)dn_qdocs, (void*)dn_skip, (void*)dn_lens, (void*)dn_up,
                     (void*)dg_ids, (void*)dg_table, (void*)dg_out, (void*)dg_shares,
                     (void*)cc_moff, (void*)cc_mem, (void*)cc_words, (void*)cc_out, (void*)cc_off,
                     (void*)td_rows, (void*)td_cnts, (void*)td_out, (void*)td_bits, (void*)td_ids, (void*)td_out_ids,
@@ -2634,6 +2658,8 @@ hipError_t grow_bytes(void** ptr, size_t* cap, size_t bytes) {
   grow_bytes(reinterpret_cast<void**>(&(ptr)), &(c)->td_cap[(slot)], (n) * sizeof(*(ptr)))
 #define rv_need(c, ptr, n, slot) \
   grow_bytes(reinterpret_cast<void**>(&(ptr)), &(c)->rv_cap[(slot)], (n) * sizeof(*(ptr)))
+#define dn_need(c, ptr, n, slot) \
+  grow_bytes(reinterpret_cast<void**>(&(ptr)), &(c)->dn_cap[(slot)], (n) * sizeof(*(ptr)))
 #define ph_need(c, ptr, n, slot) \
   grow_bytes(reinterpret_cast<void**>(&(ptr)), &(c)->ph_cap[(slot)], (n) * sizeof(*(ptr)))
 
@@ -3899,6 +3925,295 @@ lda_status lda_topic_nearest(lda_ctx* c, lda_ctx* o, int32_t metric, int32_t n, 
   HIP_TRY(hipStreamSynchronize(c->stream));
   return LDA_OK;
   });
+}
+
+namespace {
+
+// One call of lda_doc_distances (n == 0), lda_doc_nearest or
+// lda_doc_neighbors (self: the queries are the shard's own documents).
+struct DocNearCall {
+  int32_t metric = 0, n = 0;
+  bool nearest = false, self = false;
+  int64_t Q = 0;                    // queries (self: the listed documents)
+  const double* theta = nullptr;
+  const int32_t* counts = nullptr;
+  int64_t doc_begin = 0, M = 0;     // the documents of distances / neighbors
+  const int64_t* docs = nullptr;
+  const int64_t* skip = nullptr;
+  int32_t min_tokens = 1;
+  double* out = nullptr;
+  int64_t* ids = nullptr;
+  double* values = nullptr;
+};
+
+// the arguments in the order the header lists them
+lda_status check_doc_near(const lda_ctx* c, const DocNearCall& a) {
+  if (!c) return fail(LDA_ERR_INVALID_ARG, "null ctx");
+  if (a.metric < LDA_TOPIC_COSINE || a.metric > LDA_TOPIC_JS)
+    return fail(LDA_ERR_INVALID_ARG, "metric must be LDA_TOPIC_COSINE, _HELLINGER or _JS");
+  if (a.nearest && (a.n < 1 || a.n > LDA_DOC_NEAREST_MAX))
+    return fail(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_DOC_NEAREST_MAX]");
+  if (!a.self && (a.theta != nullptr) == (a.counts != nullptr))
+    return fail(LDA_ERR_INVALID_ARG, "exactly one of theta / counts must be given");
+  const bool work = a.Q > 0 && (a.nearest && !a.self ? true : a.M > 0);
+  if (work && (a.nearest ? !a.ids || !a.values : !a.out)) return fail(LDA_ERR_INVALID_ARG, "null output");
+  if (a.Q < 0 || a.M < 0) return fail(LDA_ERR_INVALID_ARG, "bad sizes");
+  if (a.docs) {
+    if (a.doc_begin != 0) return fail(LDA_ERR_INVALID_ARG, "doc_begin must be 0 with a document list");
+    for (int64_t j = 0; j < a.M; ++j)
+      if (a.docs[j] < 0 || a.docs[j] >= c->D) return fail(LDA_ERR_INVALID_ARG, "document id out of range [0, D)");
+  } else if (a.doc_begin < 0 || a.doc_begin > c->D || a.M > c->D - a.doc_begin) {
+    return fail(LDA_ERR_INVALID_ARG, "document range out of [0, D)");
+  }
+  if (a.nearest && a.min_tokens < 1) return fail(LDA_ERR_INVALID_ARG, "min_tokens must be at least 1");
+  for (int64_t q = 0; a.skip && q < a.Q; ++q)
+    if (a.skip[q] < -1 || a.skip[q] >= c->D) return fail(LDA_ERR_INVALID_ARG, "skip id out of range [-1, D)");
+  const int32_t K = c->K;
+  for (int64_t q = 0; a.theta && q < a.Q; ++q) {
+    const double* row = a.theta + (size_t)q * K;
+    double sum = 0.0, tq2 = 0.0;
+    for (int k = 0; k < K; ++k) {
+      if (!(row[k] >= 0.0) || !std::isfinite(row[k]))
+        return fail(LDA_ERR_INVALID_ARG, "theta holds a negative or non-finite entry");
+      sum += row[k];
+      tq2 += row[k] * row[k];
+    }
+    if (!(sum > 0.0) || !(tq2 > 0.0) || !std::isfinite(tq2))
+      return fail(LDA_ERR_INVALID_ARG, "a theta row sums to zero (or its squared norm leaves fp64's range)");
+  }
+  for (size_t i = 0; a.counts && i < (size_t)a.Q * (size_t)K; ++i)
+    if (a.counts[i] < 0) return fail(LDA_ERR_INVALID_ARG, "counts holds a negative entry");
+  if (c->pending) return fail(LDA_ERR_STATE, "document distances with a pending delta: call lda_apply first");
+  return LDA_OK;
+}
+
+lda_status doc_near_run(lda_ctx* c, const DocNearCall& call) {
+  const int32_t K = c->K, n = call.n;
+  const int64_t Q = call.Q;
+  // the candidates: distances' documents; every document of the shard otherwise
+  const int64_t cand_begin = call.nearest ? 0 : call.doc_begin, M = call.nearest ? c->D : call.M;
+  const int64_t* cdocs = call.nearest ? nullptr : call.docs;
+  if (Q == 0) return LDA_OK;
+  if (M == 0) {
+    if (call.nearest) {
+      std::fill(call.ids, call.ids + (size_t)Q * n, (int64_t)-1);
+      std::fill(call.values, call.values + (size_t)Q * n, std::numeric_limits<double>::quiet_NaN());
+    }
+    return LDA_OK;
+  }
+  double A = 0.0;
+  for (int k = 0; k < K; ++k) A += c->alpha[(size_t)k];
+  int64_t Qc = std::min<int64_t>(Q, DOC_NEAR_QUERIES);
+  if (g_doc_near_queries > 0) Qc = std::min(Qc, g_doc_near_queries);
+  int64_t Dc = std::min<int64_t>(M, std::max<int64_t>(1, std::min(DOC_NEAR_CELLS / Qc, DOC_NEAR_ROW_CELLS / K)));
+  if (g_doc_near_docs > 0) Dc = std::min(Dc, g_doc_near_docs);
+  auto pad = [](int64_t x) { return (x + 63) / 64 * 64; };
+  const int64_t qld_cap = pad(Qc), cld_cap = pad(Dc);
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(dn_need(c, c->dn_qrows, (size_t)(qld_cap * K), 0));
+  HIP_TRY(dn_need(c, c->dn_crows, (size_t)(cld_cap * K), 1));
+  HIP_TRY(dn_need(c, c->dn_qsums, (size_t)qld_cap, 2));
+  HIP_TRY(dn_need(c, c->dn_csums, (size_t)cld_cap, 3));
+  HIP_TRY(dn_need(c, c->dn_vals, (size_t)(Qc * Dc), 4));
+  HIP_TRY(dn_need(c, c->dn_lens, (size_t)cld_cap, 5));
+  if (cdocs) HIP_TRY(dn_need(c, c->dn_cdocs, (size_t)Dc, 6));
+  if (call.self && call.docs) HIP_TRY(dn_need(c, c->dn_qdocs, (size_t)Qc, 7));
+  if (!call.self) HIP_TRY(dn_need(c, c->dn_up, (size_t)(Qc * K), 8));
+  // the ids each query leaves out, for the whole call (uploaded per chunk)
+  const int64_t* skip = call.skip;
+  std::vector<int64_t> own;
+  if (call.self) {
+    skip = call.docs;
+    if (!skip) {
+      own = host_vector<int64_t>((size_t)Q);
+      for (int64_t q = 0; q < Q; ++q) own[(size_t)q] = call.doc_begin + q;
+      skip = own.data();
+    }
+  }
+  if (call.nearest) {
+    if (skip) HIP_TRY(dn_need(c, c->dn_skip, (size_t)Qc, 9));
+    for (int i = 0; i < 2; ++i) {
+      HIP_TRY(dn_need(c, c->dn_lids[i], (size_t)(Qc * n), 10 + 2 * i));
+      HIP_TRY(dn_need(c, c->dn_lvals[i], (size_t)(Qc * n), 11 + 2 * i));
+    }
+  }
+  const int wave_blocks = c->cus * 8;
+  auto blocks_for = [&](int64_t cols) { return (int)std::max<int64_t>(1, std::min<int64_t>((cols + 3) / 4, wave_blocks)); };
+  for (int64_t q0 = 0; q0 < Q; q0 += Qc) {
+    const int64_t qn = std::min<int64_t>(Qc, Q - q0), qld = pad(qn);
+    lda::DocRowsArgs r{};
+    r.metric = call.metric;
+    r.alpha = c->alpha_d;
+    r.A = A;
+    r.K = K;
+    r.Kp = c->Kp;
+    r.M = qn;
+    r.ld = qld;
+    r.rows = c->dn_qrows;
+    r.sums = c->dn_qsums;
+    if (call.self) {
+      r.source = lda::DOC_ROWS_Z;
+      r.z = c->z;
+      r.doc_off = c->doc_off;
+      r.doc_begin = call.doc_begin + q0;
+      if (call.docs) {
+        HIP_TRY(hipMemcpyAsync(c->dn_qdocs, call.docs + q0, sizeof(int64_t) * (size_t)qn, hipMemcpyHostToDevice,
+                               c->stream));
+        r.docs = c->dn_qdocs;
+      }
+    } else if (call.theta) {
+      r.source = lda::DOC_ROWS_THETA;
+      HIP_TRY(hipMemcpyAsync(c->dn_up, call.theta + (size_t)q0 * K, sizeof(double) * (size_t)qn * K,
+                             hipMemcpyHostToDevice, c->stream));
+      r.theta = reinterpret_cast<const double*>(c->dn_up);
+    } else {
+      r.source = lda::DOC_ROWS_COUNTS;
+      HIP_TRY(hipMemcpyAsync(c->dn_up, call.counts + (size_t)q0 * K, sizeof(int32_t) * (size_t)qn * K,
+                             hipMemcpyHostToDevice, c->stream));
+      r.counts = reinterpret_cast<const int32_t*>(c->dn_up);
+    }
+    HIP_TRY(lda::launch_doc_rows(r, blocks_for(qld), c->stream));
+    if (call.nearest && skip)
+      HIP_TRY(hipMemcpyAsync(c->dn_skip, skip + q0, sizeof(int64_t) * (size_t)qn, hipMemcpyHostToDevice, c->stream));
+    int cur = 0;
+    for (int64_t j0 = 0; j0 < M; j0 += Dc) {
+      const int64_t mn = std::min<int64_t>(Dc, M - j0), cld = pad(mn);
+      lda::DocRowsArgs cr{};
+      cr.source = lda::DOC_ROWS_Z;
+      cr.metric = call.metric;
+      cr.z = c->z;
+      cr.doc_off = c->doc_off;
+      cr.doc_begin = cand_begin + j0;
+      if (cdocs) {
+        HIP_TRY(hipMemcpyAsync(c->dn_cdocs, cdocs + j0, sizeof(int64_t) * (size_t)mn, hipMemcpyHostToDevice,
+                               c->stream));
+        cr.docs = c->dn_cdocs;
+      }
+      cr.alpha = c->alpha_d;
+      cr.A = A;
+      cr.K = K;
+      cr.Kp = c->Kp;
+      cr.M = mn;
+      cr.ld = cld;
+      cr.rows = c->dn_crows;
+      cr.sums = c->dn_csums;
+      cr.lens = c->dn_lens;
+      HIP_TRY(lda::launch_doc_rows(cr, blocks_for(cld), c->stream));
+      lda::DocPairArgs p{};
+      p.qrows = c->dn_qrows;
+      p.crows = c->dn_crows;
+      p.qsums = c->dn_qsums;
+      p.csums = c->dn_csums;
+      p.Q = qn;
+      p.M = mn;
+      p.qld = qld;
+      p.cld = cld;
+      p.ldo = mn;
+      p.K = K;
+      p.metric = call.metric;
+      p.out = c->dn_vals;
+      HIP_TRY(lda::launch_doc_pairs(p, c->stream));
+      if (!call.nearest) {
+        // rows of mn values into the caller's rows of M
+        double* dst = call.out + (size_t)q0 * M + j0;
+        if (mn == M)
+          HIP_TRY(hipMemcpyAsync(dst, c->dn_vals, sizeof(double) * (size_t)qn * mn, hipMemcpyDeviceToHost, c->stream));
+        else
+          HIP_TRY(hipMemcpy2DAsync(dst, sizeof(double) * (size_t)M, c->dn_vals, sizeof(double) * (size_t)mn,
+                                   sizeof(double) * (size_t)mn, (size_t)qn, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));   // the scratch is reused by the next chunk
+        continue;
+      }
+      lda::DocSelectArgs s{};
+      s.vals = c->dn_vals;
+      s.Q = qn;
+      s.M = mn;
+      s.ldv = mn;
+      s.id_begin = j0;
+      s.lens = c->dn_lens;
+      s.skip = skip ? c->dn_skip : nullptr;
+      s.n = n;
+      s.min_tokens = call.min_tokens;
+      s.descending = call.metric == LDA_TOPIC_COSINE;
+      s.first = j0 == 0;
+      s.in_ids = c->dn_lids[cur];
+      s.in_vals = c->dn_lvals[cur];
+      s.out_ids = c->dn_lids[cur ^ 1];
+      s.out_vals = c->dn_lvals[cur ^ 1];
+      HIP_TRY(lda::launch_doc_select(s, c->stream));
+      cur ^= 1;
+    }
+    if (call.nearest) {
+      HIP_TRY(hipMemcpyAsync(call.ids + (size_t)q0 * n, c->dn_lids[cur], sizeof(int64_t) * (size_t)qn * n,
+                             hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipMemcpyAsync(call.values + (size_t)q0 * n, c->dn_lvals[cur], sizeof(double) * (size_t)qn * n,
+                             hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(hipStreamSynchronize(c->stream));   // the scratch is reused by the next chunk
+    }
+  }
+  return LDA_OK;
+}
+
+}  // namespace
+
+lda_status lda_doc_distances(lda_ctx* c, int32_t metric, int64_t Q, const double* theta, const int32_t* counts,
+                             int64_t doc_begin, int64_t M, const int64_t* docs, double* out) {
+  return lda_abi::guarded([&]() -> lda_status {
+  DocNearCall a;
+  a.metric = metric;
+  a.Q = Q;
+  a.theta = theta;
+  a.counts = counts;
+  a.doc_begin = doc_begin;
+  a.M = M;
+  a.docs = docs;
+  a.out = out;
+  if (lda_status s = check_doc_near(c, a); s != LDA_OK) return s;
+  return doc_near_run(c, a);
+  });
+}
+
+lda_status lda_doc_nearest(lda_ctx* c, int32_t metric, int32_t n, int64_t Q, const double* theta,
+                           const int32_t* counts, const int64_t* skip, int32_t min_tokens, int64_t* doc_ids,
+                           double* values) {
+  return lda_abi::guarded([&]() -> lda_status {
+  DocNearCall a;
+  a.metric = metric;
+  a.n = n;
+  a.nearest = true;
+  a.Q = Q;
+  a.theta = theta;
+  a.counts = counts;
+  a.skip = skip;
+  a.min_tokens = min_tokens;
+  a.ids = doc_ids;
+  a.values = values;
+  if (lda_status s = check_doc_near(c, a); s != LDA_OK) return s;
+  return doc_near_run(c, a);
+  });
+}
+
+lda_status lda_doc_neighbors(lda_ctx* c, int32_t metric, int32_t n, int64_t doc_begin, int64_t M, const int64_t* docs,
+                             int32_t min_tokens, int64_t* doc_ids, double* values) {
+  return lda_abi::guarded([&]() -> lda_status {
+  DocNearCall a;
+  a.metric = metric;
+  a.n = n;
+  a.nearest = a.self = true;
+  a.Q = a.M = M;
+  a.doc_begin = doc_begin;
+  a.docs = docs;
+  a.min_tokens = min_tokens;
+  a.ids = doc_ids;
+  a.values = values;
+  if (lda_status s = check_doc_near(c, a); s != LDA_OK) return s;
+  return doc_near_run(c, a);
+  });
+}
+
+void lda_debug_doc_nearest_chunk(int64_t docs, int64_t queries) {
+  g_doc_near_docs = docs > 0 ? docs : 0;
+  g_doc_near_queries = queries > 0 ? queries : 0;
 }
 
 namespace {

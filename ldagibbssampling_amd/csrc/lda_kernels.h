@@ -499,6 +499,72 @@ struct TopicNearestArgs {
   double* values;           // [K * n]
 };
 hipError_t launch_topic_nearest(const TopicNearestArgs& a, hipStream_t st);
+// lda_doc_distances / lda_doc_nearest / lda_doc_neighbors:
+// k_topic_pairs with the roles turned -- the topics are the summed axis, the
+// documents the columns.  A side's rows live transposed in scratch,
+// rows[k * ld + j] for column j < ld (ld a multiple of 64, the columns past M
+// zero), holding p (sqrt p for Hellinger), so a tile's row segment is one
+// coalesced load.  The metrics are TOPIC_COSINE / _HELLINGER / _JS above.
+//  k_doc_rows        one wave per column.  source DOC_ROWS_Z: document
+//                    docs[j] (or doc_begin + j) of the shard, its counts in
+//                    the per-wave LDS histogram of k_doc_counts, p = ((double)
+//                    n_dk + alpha_k) / ((double) L_d + A), and lens[j] = L_d
+//                    when lens is given; DOC_ROWS_COUNTS: the same expression
+//                    of a caller's int32 row (L = its integer sum);
+//                    DOC_ROWS_THETA: a caller's fp64 row as given
+//  k_doc_row_sums    one thread per column: sum of x^2 (cosine) or of x ln x
+//                    (JS; 0 at x = 0) over k ascending from 0.0, sums[j]
+//  k_doc_pairs<m>    grid (candidate tiles, query tiles), 256 threads: a 64 x
+//                    64 tile of pairs, TOPIC_PAIR_ROWS topics at a time
+//                    through LDS, a 4 x 4 fp64 register tile per thread, each
+//                    pair's sum one chain over k ascending; closes the metric
+//                    and writes out[q * ldo + j] (+ 0.0) for q < Q, j < M
+//  k_doc_select      one wave per query: folds the chunk's values into the
+//                    query's running best-n list.  Candidates are ordered by
+//                    (monotone key of the value, document id); round i takes
+//                    the smallest pair above round i - 1's among the chunk's
+//                    columns that pass the filter (lens[j] >= min_tokens,
+//                    id_begin + j != skip[q]) and the old list, and writes
+//                    slot i of the new list (id -1, value NaN when exhausted)
+constexpr int DOC_ROWS_Z = 0, DOC_ROWS_COUNTS = 1, DOC_ROWS_THETA = 2;
+constexpr int DOC_NEAREST_MAX = 64;
+struct DocRowsArgs {
+  int32_t source, metric;
+  const int32_t* z;         // DOC_ROWS_Z
+  const int64_t* doc_off;
+  const int64_t* docs;      // [M] shard-local ids, or null: doc_begin + j
+  int64_t doc_begin;
+  const int32_t* counts;    // DOC_ROWS_COUNTS: [M * K]
+  const double* theta;      // DOC_ROWS_THETA: [M * K]
+  const double* alpha;      // [K]
+  double A;                 // alpha[0] + ... + alpha[K-1], added in that order
+  int64_t M, ld;            // columns filled, columns of the buffer (M <= ld)
+  int32_t K, Kp;
+  double* rows;             // [K * ld]
+  double* sums;             // [ld]
+  int32_t* lens;            // [ld] or null
+};
+hipError_t launch_doc_rows(const DocRowsArgs& a, int blocks, hipStream_t st);
+struct DocPairArgs {
+  const double *qrows, *crows;   // [K * qld], [K * cld]
+  const double *qsums, *csums;   // [qld], [cld]
+  int64_t Q, M, qld, cld, ldo;
+  int32_t K, metric;
+  double* out;                   // [Q * ldo]
+};
+hipError_t launch_doc_pairs(const DocPairArgs& a, hipStream_t st);
+struct DocSelectArgs {
+  const double* vals;            // [Q * ldv]
+  int64_t Q, M, ldv, id_begin;
+  const int32_t* lens;           // [M]
+  const int64_t* skip;           // [Q], -1 = none
+  int32_t n, min_tokens, descending, first;   // first: the old list is empty
+  const int64_t* in_ids;         // [Q * n]
+  const double* in_vals;
+  int64_t* out_ids;              // [Q * n]
+  double* out_vals;
+};
+hipError_t launch_doc_select(const DocSelectArgs& a, hipStream_t st);
 // range workers per block of the sampler kernel used for (C, sampler): 4
 // waves, 16 for the large-K sparse kernel (C >= 32), 8 for the half-wave
 // dense kernel (4 waves x 2 halves)

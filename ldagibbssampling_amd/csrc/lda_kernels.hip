@@ -3775,6 +3775,251 @@ __global__ __launch_bounds__(64) void k_topic_nearest(const TopicNearestArgs a) 
   }
 }
 
+// ---- lda_doc_distances / lda_doc_nearest / lda_doc_neighbors (lda_kernels.h,
+// DESIGN.md §9n)
+
+// what a side keeps per (topic, document)
+__device__ __forceinline__ double doc_row_stage(int metric, double p) {
+  return metric == TOPIC_HELLINGER ? sqrt(p) : p;
+}
+
+// One wave per column of a chunk's transposed rows.  A document's and a count
+// query's entries are one expression, ((double) c + alpha_k) / ((double) L +
+// A) with L an integer total, so equal counts give equal bits.
+__global__ __launch_bounds__(256) void k_doc_rows(const DocRowsArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int32_t h[];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  int32_t* hist = h + wid * a.Kp;
+  if (a.source == DOC_ROWS_Z) {
+    for (int i = lane; i < a.Kp; i += 64) hist[i] = 0;
+    wave_lds_fence();
+  }
+  const double* __restrict__ alpha = a.alpha;
+  for (int64_t j = (int64_t)blockIdx.x * 4 + wid; j < a.ld; j += (int64_t)gridDim.x * 4) {
+    double* __restrict__ col = a.rows + j;
+    if (j >= a.M) {   // the padding of the last tile
+      for (int k = lane; k < a.K; k += 64) col[(size_t)k * a.ld] = 0.0;
+      if (lane == 0 && a.lens) a.lens[j] = 0;
+      continue;
+    }
+    if (a.source == DOC_ROWS_Z) {
+      const int64_t d = a.docs ? a.docs[j] : a.doc_begin + j;
+      const int64_t t0 = a.doc_off[d], t1 = a.doc_off[d + 1];
+      for (int64_t i = t0 + lane; i < t1; i += 64) atomicAdd(&hist[a.z[i]], 1);
+      wave_lds_fence();
+      const double S = (double)(t1 - t0) + a.A;
+      for (int k = lane; k < a.K; k += 64)
+        col[(size_t)k * a.ld] = doc_row_stage(a.metric, ((double)hist[k] + alpha[k]) / S);
+      if (lane == 0 && a.lens) a.lens[j] = (int32_t)min(t1 - t0, (int64_t)INT32_MAX);
+      wave_lds_fence();
+      for (int k = lane; k < a.Kp; k += 64) hist[k] = 0;
+      wave_lds_fence();
+    } else if (a.source == DOC_ROWS_COUNTS) {
+      const int32_t* __restrict__ row = a.counts + (size_t)j * a.K;
+      long long tot = 0;
+      for (int k = lane; k < a.K; k += 64) tot += row[k];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t hi = (uint32_t)__shfl_xor((int)((unsigned long long)tot >> 32), o),
+                       lo = (uint32_t)__shfl_xor((int)(uint32_t)tot, o);
+        tot += (long long)(((unsigned long long)hi << 32) | lo);
+      }
+      const double S = (double)tot + a.A;
+      for (int k = lane; k < a.K; k += 64)
+        col[(size_t)k * a.ld] = doc_row_stage(a.metric, ((double)row[k] + alpha[k]) / S);
+    } else {
+      const double* __restrict__ row = a.theta + (size_t)j * a.K;
+      for (int k = lane; k < a.K; k += 64) col[(size_t)k * a.ld] = doc_row_stage(a.metric, row[k]);
+    }
+  }
+}
+
+// A column's own sum, the topics in ascending order from 0.0, its terms formed
+// as k_doc_pairs forms a pair's.
+__global__ __launch_bounds__(256) void k_doc_row_sums(const DocRowsArgs a) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= a.ld) return;
+  const double* __restrict__ col = a.rows + j;
+  double s = 0.0;
+  if (a.metric == TOPIC_COSINE) {
+    for (int k = 0; k < a.K; ++k) {
+      const double x = col[(size_t)k * a.ld];
+      s += x * x;
+    }
+  } else {
+    for (int k = 0; k < a.K; ++k) {
+      const double x = col[(size_t)k * a.ld];
+      s += x > 0.0 ? x * log(x) : 0.0;
+    }
+  }
+  a.sums[j] = s;
+}
+
+template <int METRIC>
+__device__ __forceinline__ double doc_term(double x, double y) {
+  if constexpr (METRIC == TOPIC_HELLINGER) {
+    const double d = x - y;
+    return d * d;
+  } else if constexpr (METRIC == TOPIC_JS) {
+    const double s = x + y;
+    return s > 0.0 ? s * log(0.5 * s) : 0.0;
+  } else {
+    return x * y;
+  }
+}
+
+// One 64 x 64 tile of (query, candidate) pairs.  Thread t loads column t & 63
+// of topics (t >> 6) + 4 u of each side (coalesced 512-byte row segments) and
+// accumulates the pairs q = ty + 16 i, c = tx + 16 j in a 4 x 4 fp64 register
+// tile, as k_topic_pairs does.  The next step's values are loaded into
+// registers while this one is summed.  A pair's sum is one chain over k
+// ascending, so it is a function of the two rows alone.
+template <int METRIC>
+__global__ __launch_bounds__(256) void k_doc_pairs(const DocPairArgs a) {
+  __shared__ double As[TOPIC_PAIR_ROWS][64], Bs[TOPIC_PAIR_ROWS][64];
+  const int tb = blockIdx.x, ta = blockIdx.y;
+  constexpr int PER = TOPIC_PAIR_ROWS / 4;
+  const int tid = threadIdx.x, col = tid & 63, r0 = tid >> 6, tx = tid & 15, ty = tid >> 4;
+  const double* __restrict__ qa = a.qrows + (size_t)ta * 64 + col;   // < qld
+  const double* __restrict__ cb = a.crows + (size_t)tb * 64 + col;   // < cld
+  const int K = a.K;
+  double na[PER], nb[PER];
+  auto fetch = [&](int k) {
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      const int row = k + r0 + 4 * u;
+      na[u] = row < K ? qa[(size_t)row * a.qld] : 0.0;
+      nb[u] = row < K ? cb[(size_t)row * a.cld] : 0.0;
+    }
+  };
+  double acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
+  fetch(0);
+  for (int k = 0; k < K; k += TOPIC_PAIR_ROWS) {
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+      As[r0 + 4 * u][col] = na[u];
+      Bs[r0 + 4 * u][col] = nb[u];
+    }
+    __syncthreads();
+    if (k + TOPIC_PAIR_ROWS < K) fetch(k + TOPIC_PAIR_ROWS);
+    const int rows = min(TOPIC_PAIR_ROWS, K - k);   // topics past K are never summed
+    for (int r = 0; r < rows; ++r) {
+      double x[4], y[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        x[i] = As[r][ty + 16 * i];
+        y[i] = Bs[r][tx + 16 * i];
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] += doc_term<METRIC>(x[i], y[j]);
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int64_t q = (int64_t)ta * 64 + ty + 16 * i;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t c = (int64_t)tb * 64 + tx + 16 * j;
+      if (q < a.Q && c < a.M) {
+        const double S = acc[i][j];
+        double v;
+        if constexpr (METRIC == TOPIC_COSINE)
+          v = S / sqrt(a.csums[c] * a.qsums[q]);
+        else if constexpr (METRIC == TOPIC_HELLINGER)
+          v = sqrt(fmin(1.0, 0.5 * S));
+        else
+          v = fmax(0.0, 0.5 * ((a.csums[c] + a.qsums[q]) - S));
+        a.out[(size_t)q * a.ldo + c] = v + 0.0;
+      }
+    }
+  }
+}
+
+// The order key of a value: its bit pattern made monotone (k_topic_nearest),
+// complemented for a descending order; and back.
+__device__ __forceinline__ unsigned long long doc_order_key(double v, int descending) {
+  unsigned long long u = (unsigned long long)__double_as_longlong(v + 0.0);
+  u = (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+  return descending ? ~u : u;
+}
+__device__ __forceinline__ double doc_order_value(unsigned long long u, int descending) {
+  if (descending) u = ~u;
+  u = (u >> 63) ? (u & 0x7FFFFFFFFFFFFFFFull) : ~u;
+  return __longlong_as_double((long long)u);
+}
+
+__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int o) {
+  const uint32_t hi = (uint32_t)__shfl_xor((int)(v >> 32), o), lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// lda_doc_nearest's selection: one wave per query.  Round i takes the
+// smallest (key, id) above round i - 1's among the chunk's columns that pass
+// the filter and the entries of the old list -- lane l scans columns l, l +
+// 64, ... and list slot l -- then a wave-wide minimum.  The new list is the
+// best n of the old list and the chunk, so after the last chunk it is the
+// best n of all candidates however they were cut.
+__global__ __launch_bounds__(64) void k_doc_select(const DocSelectArgs a) {
+  const int lane = threadIdx.x, n = a.n;
+  const int64_t q = blockIdx.x;
+  const double* __restrict__ v = a.vals + (size_t)q * a.ldv;
+  const int32_t* __restrict__ lens = a.lens;
+  const int64_t skip = a.skip ? a.skip[q] : -1;
+  constexpr long long NONE = 0x7FFFFFFFFFFFFFFFll;
+  unsigned long long pk = 0;
+  long long pid = -1;   // every candidate is above (0, -1)
+  unsigned long long lk = 0;
+  long long lid = -1;   // this lane's slot of the old list
+  if (!a.first && lane < n) {
+    lid = a.in_ids[(size_t)q * n + lane];
+    if (lid >= 0) lk = doc_order_key(a.in_vals[(size_t)q * n + lane], a.descending);
+  }
+  for (int i = 0; i < n; ++i) {
+    unsigned long long bk = ~0ull;
+    long long bid = NONE;
+    for (int64_t b = lane; b < a.M; b += 64) {
+      const long long id = a.id_begin + b;
+      if (lens[b] < a.min_tokens || id == skip) continue;
+      const unsigned long long u = doc_order_key(v[b], a.descending);
+      const bool after = u > pk || (u == pk && id > pid);
+      if (after && (u < bk || (u == bk && id < bid))) {
+        bk = u;
+        bid = id;
+      }
+    }
+    if (lid >= 0) {
+      const bool after = lk > pk || (lk == pk && lid > pid);
+      if (after && (lk < bk || (lk == bk && lid < bid))) {
+        bk = lk;
+        bid = lid;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long ok = shfl_xor_u64(bk, o);
+      const long long oid = (long long)shfl_xor_u64((unsigned long long)bid, o);
+      if (ok < bk || (ok == bk && oid < bid)) {
+        bk = ok;
+        bid = oid;
+      }
+    }
+    if (lane == 0) {
+      a.out_ids[(size_t)q * n + i] = bid == NONE ? -1 : bid;
+      a.out_vals[(size_t)q * n + i] =
+          bid == NONE ? __longlong_as_double(0x7FF8000000000000ll) : doc_order_value(bk, a.descending);
+    }
+    pk = bk;
+    pid = bid;
+  }
+}
+
 // lda_heldout_loglik: inv[k] = 1 / (nwsum[k] + V beta) in fp64, 0 for the
 // padded topics.
 __global__ __launch_bounds__(256) void k_heldout_inv(const int32_t* __restrict__ nwsum, double vbeta, int32_t K,
@@ -5008,6 +5253,42 @@ hipError_t launch_topic_dist_final(const TopicPairArgs& a, hipStream_t st) {
 hipError_t launch_topic_nearest(const TopicNearestArgs& a, hipStream_t st) {
   if (a.K < 1 || a.K2 < 1 || a.n < 1 || a.n > 64) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_topic_nearest, dim3(a.K), dim3(64), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_doc_rows(const DocRowsArgs& a, int blocks, hipStream_t st) {
+  if (a.ld <= 0) return hipSuccess;
+  if (a.M < 0 || a.M > a.ld || a.ld % 64 || a.K < 1 || a.K > a.Kp || a.Kp % 64 || blocks < 1 ||
+      a.source < DOC_ROWS_Z || a.source > DOC_ROWS_THETA || a.metric < TOPIC_COSINE || a.metric > TOPIC_JS)
+    return hipErrorInvalidValue;
+  const size_t lds = a.source == DOC_ROWS_Z ? 4 * (size_t)a.Kp * sizeof(int32_t) : 0;
+  hipLaunchKernelGGL(k_doc_rows, dim3(blocks), dim3(256), lds, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || a.metric == TOPIC_HELLINGER) return e;
+  hipLaunchKernelGGL(k_doc_row_sums, dim3((unsigned)((a.ld + 255) / 256)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_doc_pairs(const DocPairArgs& a, hipStream_t st) {
+  if (a.Q <= 0 || a.M <= 0) return hipSuccess;
+  const int64_t tq = (a.Q + 63) / 64, tc = (a.M + 63) / 64;
+  if (a.K < 1 || a.qld % 64 || a.cld % 64 || tq * 64 > a.qld || tc * 64 > a.cld || a.ldo < a.M || tq > 65535 ||
+      tc > 0x7FFFFFFF)
+    return hipErrorInvalidValue;
+  const dim3 grid((unsigned)tc, (unsigned)tq);
+  switch (a.metric) {
+    case TOPIC_COSINE: hipLaunchKernelGGL(k_doc_pairs<TOPIC_COSINE>, grid, dim3(256), 0, st, a); break;
+    case TOPIC_HELLINGER: hipLaunchKernelGGL(k_doc_pairs<TOPIC_HELLINGER>, grid, dim3(256), 0, st, a); break;
+    case TOPIC_JS: hipLaunchKernelGGL(k_doc_pairs<TOPIC_JS>, grid, dim3(256), 0, st, a); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_doc_select(const DocSelectArgs& a, hipStream_t st) {
+  if (a.Q <= 0) return hipSuccess;
+  if (a.n < 1 || a.n > DOC_NEAREST_MAX || a.M < 0 || a.ldv < a.M || a.Q > 0x7FFFFFFF) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_doc_select, dim3((unsigned)a.Q), dim3(64), 0, st, a);
   return hipGetLastError();
 }
 

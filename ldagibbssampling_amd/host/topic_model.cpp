@@ -1059,6 +1059,185 @@ void ParallelTopicModel::nearestTopics(ParallelTopicModel* other, int32_t metric
         "lda_topic_nearest");
 }
 
+namespace {
+// the arguments of documentDistances / nearestDocuments / documentNeighbors
+// (n null: no n; own: the queries are the model's documents), in
+// lda_doc_distances' order, before any shard is built.  Without a list the
+// documents are all D of them.
+void checkDocNear(int32_t K, int64_t D, int32_t metric, const int32_t* n, bool own, const double* theta,
+                  const int32_t* counts, bool outputs, int64_t Q, int64_t M, const int64_t* docs,
+                  const int32_t* min_tokens, const int64_t* skip) {
+  if (metric < LDA_TOPIC_COSINE || metric > LDA_TOPIC_JS)
+    raise(LDA_ERR_INVALID_ARG, "metric must be LDA_TOPIC_COSINE, _HELLINGER or _JS");
+  if (n && (*n < 1 || *n > LDA_DOC_NEAREST_MAX)) raise(LDA_ERR_INVALID_ARG, "n must be in [1, LDA_DOC_NEAREST_MAX]");
+  if (!own && (theta != nullptr) == (counts != nullptr))
+    raise(LDA_ERR_INVALID_ARG, "exactly one of theta / counts must be given");
+  const bool nearest = n && !own;
+  if (Q > 0 && (nearest || M > 0) && !outputs) raise(LDA_ERR_INVALID_ARG, "null output");
+  if (Q < 0 || M < 0) raise(LDA_ERR_INVALID_ARG, "bad sizes");
+  if (!nearest) {
+    if (!docs && M != D) raise(LDA_ERR_INVALID_ARG, "without a document list M must be the number of documents");
+    for (int64_t j = 0; docs && j < M; ++j)
+      if (docs[j] < 0 || docs[j] >= D) raise(LDA_ERR_INVALID_ARG, "document id out of range [0, D)");
+  }
+  if (min_tokens && *min_tokens < 1) raise(LDA_ERR_INVALID_ARG, "min_tokens must be at least 1");
+  for (int64_t q = 0; skip && q < Q; ++q)
+    if (skip[q] < -1 || skip[q] >= D) raise(LDA_ERR_INVALID_ARG, "skip id out of range [-1, D)");
+  for (int64_t q = 0; theta && q < Q; ++q) {
+    const double* row = theta + (size_t)q * K;
+    double sum = 0.0, tq2 = 0.0;
+    for (int k = 0; k < K; ++k) {
+      if (!(row[k] >= 0.0) || !std::isfinite(row[k]))
+        raise(LDA_ERR_INVALID_ARG, "theta holds a negative or non-finite entry");
+      sum += row[k];
+      tq2 += row[k] * row[k];
+    }
+    if (!(sum > 0.0) || !(tq2 > 0.0) || !std::isfinite(tq2))
+      raise(LDA_ERR_INVALID_ARG, "a theta row sums to zero (or its squared norm leaves fp64's range)");
+  }
+  for (size_t i = 0; counts && i < (size_t)Q * (size_t)K; ++i)
+    if (counts[i] < 0) raise(LDA_ERR_INVALID_ARG, "counts holds a negative entry");
+}
+
+// queries per round of documentNeighbors over several shards
+constexpr int64_t NEIGHBOR_QUERIES = 1024;
+}  // namespace
+
+void ParallelTopicModel::documentDistances(int32_t metric, int64_t Q, const double* theta, const int32_t* counts,
+                                           int64_t M, const int64_t* docs, double* out) {
+  checkDocNear(K_, numDocs(), metric, nullptr, false, theta, counts, out != nullptr, Q, M, docs, nullptr, nullptr);
+  if (Q == 0 || M == 0) return;
+  ensureShards();
+  const std::vector<int64_t>& begin = shards_->doc_begin;
+  const size_t G = shards_->ctx.size();
+  std::vector<double> part;
+  if (!docs) {
+    for (size_t g = 0; g < G; ++g) {
+      const int64_t d0 = begin[g], m = begin[g + 1] - d0;
+      if (m == 0) continue;
+      if (G == 1) {
+        check(lda_doc_distances(shards_->ctx[g], metric, Q, theta, counts, 0, m, nullptr, out), "lda_doc_distances");
+        return;
+      }
+      part.resize((size_t)Q * m);
+      check(lda_doc_distances(shards_->ctx[g], metric, Q, theta, counts, 0, m, nullptr, part.data()),
+            "lda_doc_distances");
+      for (int64_t q = 0; q < Q; ++q) std::copy(part.begin() + q * m, part.begin() + (q + 1) * m, out + q * M + d0);
+    }
+    return;
+  }
+  // the list's documents by shard (shard-local ids), and where each goes in
+  // the caller's order
+  std::vector<std::vector<int64_t>> local(G), pos(G);
+  for (int64_t j = 0; j < M; ++j) {
+    const size_t g = (size_t)(std::upper_bound(begin.begin(), begin.end(), docs[j]) - begin.begin()) - 1;
+    local[g].push_back(docs[j] - begin[g]);
+    pos[g].push_back(j);
+  }
+  for (size_t g = 0; g < G; ++g) {
+    const int64_t m = (int64_t)local[g].size();
+    if (m == 0) continue;
+    part.resize((size_t)Q * m);
+    check(lda_doc_distances(shards_->ctx[g], metric, Q, theta, counts, 0, m, local[g].data(), part.data()),
+          "lda_doc_distances");
+    for (int64_t q = 0; q < Q; ++q)
+      for (int64_t i = 0; i < m; ++i) out[q * M + pos[g][(size_t)i]] = part[(size_t)(q * m + i)];
+  }
+}
+
+void ParallelTopicModel::nearestDocuments(int32_t metric, int32_t n, int64_t Q, const double* theta,
+                                          const int32_t* counts, const int64_t* skip, int32_t min_tokens,
+                                          int64_t* doc_ids, double* values) {
+  checkDocNear(K_, numDocs(), metric, &n, false, theta, counts, doc_ids && values, Q, 0, nullptr, &min_tokens, skip);
+  if (Q == 0) return;
+  ensureShards();
+  const std::vector<int64_t>& begin = shards_->doc_begin;
+  const size_t G = shards_->ctx.size(), cells = (size_t)Q * (size_t)n;
+  if (G == 1) {
+    check(lda_doc_nearest(shards_->ctx[0], metric, n, Q, theta, counts, skip, min_tokens, doc_ids, values),
+          "lda_doc_nearest");
+    return;
+  }
+  std::vector<int64_t> ids(G * cells), local((size_t)Q);
+  std::vector<double> vals(G * cells);
+  for (size_t g = 0; g < G; ++g) {
+    for (int64_t q = 0; skip && q < Q; ++q)
+      local[(size_t)q] = skip[q] >= begin[g] && skip[q] < begin[g + 1] ? skip[q] - begin[g] : -1;
+    check(lda_doc_nearest(shards_->ctx[g], metric, n, Q, theta, counts, skip ? local.data() : nullptr, min_tokens,
+                          ids.data() + g * cells, vals.data() + g * cells),
+          "lda_doc_nearest");
+  }
+  // per query the best n of the shards' candidates by (value in the metric's
+  // order, global id ascending); the values are the device's bits
+  const bool descending = metric == LDA_TOPIC_COSINE;
+  std::vector<std::pair<double, int64_t>> cand;
+  for (int64_t q = 0; q < Q; ++q) {
+    cand.clear();
+    for (size_t g = 0; g < G; ++g)
+      for (int32_t i = 0; i < n; ++i) {
+        const size_t at = g * cells + (size_t)q * n + i;
+        if (ids[at] < 0) break;
+        cand.emplace_back(vals[at], ids[at] + begin[g]);
+      }
+    std::sort(cand.begin(), cand.end(), [descending](const auto& a, const auto& b) {
+      if (a.first != b.first) return descending ? a.first > b.first : a.first < b.first;
+      return a.second < b.second;
+    });
+    for (int32_t i = 0; i < n; ++i) {
+      const size_t o = (size_t)q * n + i;
+      const bool has = (size_t)i < cand.size();
+      doc_ids[o] = has ? cand[(size_t)i].second : -1;
+      values[o] = has ? cand[(size_t)i].first : std::numeric_limits<double>::quiet_NaN();
+    }
+  }
+}
+
+void ParallelTopicModel::documentNeighbors(int32_t metric, int32_t n, int64_t M, const int64_t* docs,
+                                           int32_t min_tokens, int64_t* doc_ids, double* values) {
+  checkDocNear(K_, numDocs(), metric, &n, true, nullptr, nullptr, doc_ids && values, M, M, docs, &min_tokens, nullptr);
+  if (M == 0) return;
+  ensureShards();
+  if (shards_->ctx.size() == 1) {
+    check(lda_doc_neighbors(shards_->ctx[0], metric, n, 0, M, docs, min_tokens, doc_ids, values),
+          "lda_doc_neighbors");
+    return;
+  }
+  std::vector<int64_t> own;
+  std::vector<int32_t> nd;
+  for (int64_t q0 = 0; q0 < M; q0 += NEIGHBOR_QUERIES) {
+    const int64_t qn = std::min<int64_t>(NEIGHBOR_QUERIES, M - q0);
+    own.resize((size_t)qn);
+    for (int64_t q = 0; q < qn; ++q) own[(size_t)q] = docs ? docs[q0 + q] : q0 + q;
+    nd.resize((size_t)qn * K_);
+    docCounts(qn, own.data(), nd.data());
+    nearestDocuments(metric, n, qn, nullptr, nd.data(), own.data(), min_tokens, doc_ids + q0 * n, values + q0 * n);
+  }
+}
+
+std::string documentNeighborsFormat(int64_t M, int32_t n, const int64_t* docs, const int64_t* doc_ids,
+                                    const double* values, const std::function<std::string(int64_t)>& name) {
+  std::string out = "#doc neighbor name value\n";
+  for (int64_t j = 0; j < M; ++j)
+    for (int32_t i = 0; i < n; ++i) {
+      const size_t at = (size_t)j * n + i;
+      if (doc_ids[at] < 0) break;
+      out += std::to_string(docs ? docs[j] : j) + " " + std::to_string(doc_ids[at]) + " " + name(doc_ids[at]) + " " +
+             java_double(values[at]) + "\n";
+    }
+  return out;
+}
+
+std::string ParallelTopicModel::documentNeighborsText(int32_t n, int32_t metric, int32_t min_tokens) {
+  const int64_t D = numDocs();
+  checkDocNear(K_, D, metric, &n, true, nullptr, nullptr, true, D, D, nullptr, &min_tokens, nullptr);
+  std::vector<int64_t> ids((size_t)D * n);
+  std::vector<double> vals((size_t)D * n);
+  documentNeighbors(metric, n, D, nullptr, min_tokens, ids.data(), vals.data());
+  return documentNeighborsFormat(D, n, nullptr, ids.data(), vals.data(), [&](int64_t d) {
+    return has_source_[(size_t)d] ? sources_[(size_t)d] : std::string("null-source");
+  });
+}
+
 void ParallelTopicModel::docReadout(int32_t mtop, int64_t M, const int64_t* docs, int32_t* out0, int32_t* out1) {
   if (M < 0) raise(LDA_ERR_INVALID_ARG, "bad sizes");
   const int64_t D = numDocs();
@@ -2891,6 +3070,57 @@ lda_status ldatm_topic_documents_format(int32_t K, int32_t n, double smoothing, 
   std::string s;
   lda_status st = guard([&] {
     s = lda_host::topicDocumentsFormat(K, n, smoothing, doc_ids, counts, lengths, [&](int64_t d) {
+      return d < num_names && names[d] ? std::string(names[d]) : std::string("null-source");
+    });
+  });
+  return st ? st : copy_text(s, buf, cap, len);
+}
+
+lda_status ldatm_document_distances(ldatm* m, int32_t metric, int64_t Q, const double* theta, const int32_t* counts,
+                                    int64_t M, const int64_t* docs, double* out) {
+  TM_CHECK(m);
+  return guard([&] { m->model.documentDistances(metric, Q, theta, counts, M, docs, out); });
+}
+
+lda_status ldatm_nearest_documents(ldatm* m, int32_t metric, int32_t n, int64_t Q, const double* theta,
+                                   const int32_t* counts, const int64_t* skip, int32_t min_tokens, int64_t* doc_ids,
+                                   double* values) {
+  TM_CHECK(m);
+  return guard([&] { m->model.nearestDocuments(metric, n, Q, theta, counts, skip, min_tokens, doc_ids, values); });
+}
+
+lda_status ldatm_document_neighbors(ldatm* m, int32_t metric, int32_t n, int64_t M, const int64_t* docs,
+                                    int32_t min_tokens, int64_t* doc_ids, double* values) {
+  TM_CHECK(m);
+  return guard([&] { m->model.documentNeighbors(metric, n, M, docs, min_tokens, doc_ids, values); });
+}
+
+lda_status ldatm_document_neighbors_text(ldatm* m, int32_t n, int32_t metric, int32_t min_tokens, char* buf,
+                                         size_t cap, size_t* len) {
+  TM_CHECK(m);
+  std::string s;
+  lda_status st = guard([&] { s = m->model.documentNeighborsText(n, metric, min_tokens); });
+  return st ? st : copy_text(s, buf, cap, len);
+}
+
+lda_status ldatm_print_document_neighbors(ldatm* m, const char* path, int32_t n, int32_t metric,
+                                          int32_t min_tokens) {
+  TM_CHECK(m);
+  std::string s;
+  lda_status st = guard([&] { s = m->model.documentNeighborsText(n, metric, min_tokens); });
+  return st ? st : write_file(path, s);
+}
+
+lda_status ldatm_document_neighbors_format(int64_t M, int32_t n, const int64_t* docs, const int64_t* doc_ids,
+                                           const double* values, const char* const* names, int64_t num_names,
+                                           char* buf, size_t cap, size_t* len) {
+  if (M < 0 || n < 1 || (M > 0 && (!doc_ids || !values)) || num_names < 0 || (num_names > 0 && !names)) {
+    g_tm_error = "bad argument";
+    return LDA_ERR_INVALID_ARG;
+  }
+  std::string s;
+  lda_status st = guard([&] {
+    s = lda_host::documentNeighborsFormat(M, n, docs, doc_ids, values, [&](int64_t d) {
       return d < num_names && names[d] ? std::string(names[d]) : std::string("null-source");
     });
   });

@@ -47,6 +47,12 @@ void coherenceFinish(int32_t K, int32_t n, int32_t measure, double epsilon, cons
 double topicDocWeight(int32_t K, double smoothing, int32_t count, int32_t length);
 std::string topicDocumentsFormat(int32_t K, int32_t n, double smoothing, const int64_t* doc_ids, const int32_t* counts,
                                  const int32_t* lengths, const std::function<std::string(int64_t)>& name);
+// printDocumentNeighbors' text from M x n arrays: "#doc neighbor name value",
+// then "<doc> <neighbor> <name of the neighbor> <value>" per query document
+// docs[j] (null: j) and rank, Java Double.toString values; a query's list
+// ends at its first id < 0 (host only; ldatm_document_neighbors_format)
+std::string documentNeighborsFormat(int64_t M, int32_t n, const int64_t* docs, const int64_t* doc_ids,
+                                    const double* values, const std::function<std::string(int64_t)>& name);
 
 // ldatm_relevant_words_format's relevance, logprob - (1 - lambda) (logprob -
 // loglift), and its text from K x n lists (host only, no device)
@@ -261,6 +267,29 @@ class ParallelTopicModel {
   // before any shard is built.
   void topicDistances(ParallelTopicModel* other, int32_t metric, double* out);
   void nearestTopics(ParallelTopicModel* other, int32_t metric, int32_t n, int32_t* topics, double* values);
+
+  // ---- nearest documents ---------------------------------
+  // lda_doc_distances routed to the shards as scoreTheta routes: queries
+  // theta[Q*K] or counts[Q*K] (exactly one) against the global document ids
+  // docs[M] (null: every document, M = numDocs()); out [Q*M]
+  void documentDistances(int32_t metric, int64_t Q, const double* theta, const int32_t* counts, int64_t M,
+                         const int64_t* docs, double* out);
+  // lda_doc_nearest on every shard among its own documents (skip: global ids,
+  // -1 or null = none), the local ids made global and the shards' Q x n lists
+  // merged by (value, global id).  A shard's list holds each of its documents
+  // that belongs to the global best n, so the result does not depend on the
+  // number of shards, bit for bit.  doc_ids / values [Q*n], -1 / NaN past the
+  // last candidate
+  void nearestDocuments(int32_t metric, int32_t n, int64_t Q, const double* theta, const int32_t* counts,
+                        const int64_t* skip, int32_t min_tokens, int64_t* doc_ids, double* values);
+  // the queries are the model's own documents docs[M] (null: all).  One
+  // shard: lda_doc_neighbors passed through.  Several: per chunk of queries
+  // docCounts from the owning shards, then nearestDocuments(counts, skip = own
+  // id); the same bits by lda_doc_neighbors' contract
+  void documentNeighbors(int32_t metric, int32_t n, int64_t M, const int64_t* docs, int32_t min_tokens,
+                         int64_t* doc_ids, double* values);
+  // documentNeighbors of every document as text (documentNeighborsFormat)
+  std::string documentNeighborsText(int32_t n, int32_t metric, int32_t min_tokens);
 
   // ---- outputs -------------------------------------------------------
   std::string documentTopics(double threshold, int32_t max);

@@ -749,6 +749,66 @@ class GibbsSampler:
                    "lda_topic_nearest")
         return topics, values
 
+    def doc_distances(self, metric, theta=None, counts=None, docs=None, doc_begin: int = 0,
+                      num_docs: int | None = None) -> np.ndarray:
+        """lda_doc_distances: the float64 (Q, M) matrix of a metric ("cosine",
+        a similarity; "hellinger"; "jensen_shannon", nats; or the integer)
+        between query rows and the topic distributions p_d = (n_dk + alpha_k) /
+        (L_d + A) of this shard's documents, computed on the device from z.
+        Queries: theta[Q, K] used as given, or counts[Q, K] (int32) turned into
+        (c_k + alpha_k) / (sum c + A) on the device -- exactly one of them.
+        docs as score_docs takes them."""
+        m = capi.doc_metric(metric)
+        theta, counts = capi.doc_queries(theta, counts, self.K)
+        q = theta if theta is not None else counts
+        begin, M, ids = self._doc_list(docs, doc_begin, num_docs)
+        out = np.zeros((len(q), max(M, 0)), dtype=np.float64)
+        capi.check(self._L.lda_doc_distances(self._h, m, len(q), theta.ctypes.data if theta is not None else None,
+                                             counts.ctypes.data if counts is not None else None, begin, M,
+                                             ids.ctypes.data if ids is not None and M else None, out.ctypes.data),
+                   "lda_doc_distances")
+        return out
+
+    def nearest_docs(self, n: int, metric="hellinger", theta=None, counts=None, skip=None, min_tokens: int = 1):
+        """lda_doc_nearest: per query row (theta or counts, as doc_distances
+        takes them) the n nearest of this shard's documents with at least
+        min_tokens tokens, selected on the device: value ascending (cosine:
+        descending), equal values by ascending document id.  skip[Q] names a
+        document each query leaves out (-1: none).  Returns (docs int64 (Q, n),
+        values float64 (Q, n)); slots past the last candidate hold -1 / NaN."""
+        n = capi.doc_nearest_n(n)
+        m = capi.doc_metric(metric)
+        theta, counts = capi.doc_queries(theta, counts, self.K)
+        q = theta if theta is not None else counts
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, dtype=np.int64).reshape(-1)
+            if len(sk) != len(q):
+                raise ValueError(f"skip must hold one id per query ({len(q)}), not {len(sk)}")
+        ids = np.zeros((len(q), n), dtype=np.int64)
+        values = np.zeros((len(q), n), dtype=np.float64)
+        capi.check(self._L.lda_doc_nearest(self._h, m, n, len(q), theta.ctypes.data if theta is not None else None,
+                                           counts.ctypes.data if counts is not None else None,
+                                           sk.ctypes.data if sk is not None and len(sk) else None, int(min_tokens),
+                                           ids.ctypes.data, values.ctypes.data), "lda_doc_nearest")
+        return ids, values
+
+    def doc_neighbors(self, n: int, metric="hellinger", docs=None, min_tokens: int = 1):
+        """lda_doc_neighbors: per listed document of this shard (None: all) its
+        n nearest other documents with at least min_tokens tokens; the query
+        rows are built on the device from z.  Bit-identical to doc_counts
+        followed by nearest_docs(counts=..., skip=own id).  Returns (docs int64
+        (M, n), values float64 (M, n))."""
+        n = capi.doc_nearest_n(n)
+        m = capi.doc_metric(metric)
+        begin, M, ids = self._doc_list(docs, 0, None)
+        out = np.zeros((M, n), dtype=np.int64)
+        values = np.zeros((M, n), dtype=np.float64)
+        capi.check(self._L.lda_doc_neighbors(self._h, m, n, begin, M, ids.ctypes.data if ids is not None and M else None,
+                                             int(min_tokens), out.ctypes.data, values.ctypes.data),
+                   "lda_doc_neighbors")
+        return out, values
+
     def heldout_loglik(self, theta, doc_off, words):
         """lda_heldout_loglik: the log likelihood of the scored tokens of Dh
         held-out documents (doc_off[Dh + 1], words) under their topic

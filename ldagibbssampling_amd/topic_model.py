@@ -91,6 +91,13 @@ TM_SIGNATURES = {
                                           C.POINTER(C.c_size_t)]),
     "ldatm_print_top_words": (_i32, [_vp, C.c_char_p, _i32, _i32]),
     "ldatm_top_words_text": (_i32, [_vp, _i32, _i32, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ldatm_document_distances": (_i32, [_vp, _i32, C.c_int64, _vp, _vp, C.c_int64, _vp, _vp]),
+    "ldatm_nearest_documents": (_i32, [_vp, _i32, _i32, C.c_int64, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "ldatm_document_neighbors": (_i32, [_vp, _i32, _i32, C.c_int64, _vp, _i32, _vp, _vp]),
+    "ldatm_document_neighbors_text": (_i32, [_vp, _i32, _i32, _i32, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "ldatm_print_document_neighbors": (_i32, [_vp, C.c_char_p, _i32, _i32, _i32]),
+    "ldatm_document_neighbors_format": (_i32, [C.c_int64, _i32, _vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_size_t,
+                                               C.POINTER(C.c_size_t)]),
     "ldatm_topic_top_docs": (_i32, [_vp, _i32, C.c_double, _i32, _vp, _vp, _vp]),
     "ldatm_relevant_words": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ldatm_salient_words": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp]),
@@ -207,6 +214,34 @@ def format_topic_documents(docs, counts, lengths, smoothing: float = 10.0, names
     _check(L.ldatm_topic_documents_format(*args, None, 0, C.byref(size)), "ldatm_topic_documents_format")
     buf = C.create_string_buffer(size.value + 1)
     _check(L.ldatm_topic_documents_format(*args, buf, size.value + 1, C.byref(size)), "ldatm_topic_documents_format")
+    return buf.value.decode()
+
+
+def format_document_neighbors(neighbors, values, docs=None, names=None) -> str:
+    """ldatm_document_neighbors_format (host only, no device):
+    printDocumentNeighbors' text from [M, n] arrays as documentNeighbors returns
+    them; docs[M] are the query documents (None: 0 .. M-1), names[d] document
+    d's name column (None, or no entry: "null-source")."""
+    ids = np.ascontiguousarray(neighbors, np.int64)
+    vals = np.ascontiguousarray(values, np.float64)
+    if ids.ndim != 2 or vals.shape != ids.shape or ids.shape[1] < 1:
+        raise ValueError("neighbors and values must be [M, n] arrays of one shape, n >= 1")
+    M, n = ids.shape
+    q = None
+    if docs is not None:
+        q = np.ascontiguousarray(docs, np.int64).reshape(-1)
+        if len(q) != M:
+            raise ValueError(f"docs must hold one id per row ({M})")
+    names = list(names or [])
+    arr = (C.c_char_p * max(len(names), 1))(*[None if s is None else str(s).encode() for s in names])
+    L = load_tm()
+    size = C.c_size_t()
+    args = (M, n, q.ctypes.data if q is not None and M else None, ids.ctypes.data if M else None,
+            vals.ctypes.data if M else None, C.cast(arr, C.c_void_p), len(names))
+    _check(L.ldatm_document_neighbors_format(*args, None, 0, C.byref(size)), "ldatm_document_neighbors_format")
+    buf = C.create_string_buffer(size.value + 1)
+    _check(L.ldatm_document_neighbors_format(*args, buf, size.value + 1, C.byref(size)),
+           "ldatm_document_neighbors_format")
     return buf.value.decode()
 
 
@@ -1539,6 +1574,82 @@ class ParallelTopicModel:
                                        scores.ctypes.data), "topDocuments")
         return ids, scores
 
+    # ------------------------------------------ nearest documents
+    def documentDistances(self, theta=None, counts=None, docs=None, metric="hellinger") -> np.ndarray:
+        """ldatm_document_distances: the float64 (Q, M) matrix of a metric
+        ("cosine", "hellinger", "jensen_shannon" or the integer) between query
+        rows -- theta[Q, K] as given, or counts[Q, K] smoothed with the model's
+        alpha on the device; exactly one -- and the training documents `docs`
+        (global ids, any order; None = all), computed on the device."""
+        m = capi.doc_metric(metric)
+        theta, counts = capi.doc_queries(theta, counts, self.numTopics)
+        q = theta if theta is not None else counts
+        ids, M = _doc_ids(docs, self)
+        out = np.zeros((len(q), M), np.float64)
+        _check(self._L.ldatm_document_distances(self._h, m, len(q), theta.ctypes.data if theta is not None else None,
+                                                counts.ctypes.data if counts is not None else None, M,
+                                                ids.ctypes.data if ids is not None and M else None,
+                                                out.ctypes.data), "documentDistances")
+        return out
+
+    def nearestDocuments(self, theta=None, n: int = 10, metric="hellinger", minTokens: int = 1, counts=None,
+                         skip=None):
+        """ldatm_nearest_documents: per query row (theta or counts, as
+        documentDistances takes them) the n nearest training documents with at
+        least minTokens tokens, selected on the device: value ascending
+        (cosine: descending), ties by ascending id; skip[Q] names a document
+        each query leaves out (-1: none).  Returns (docs int64 (Q, n), values
+        float64 (Q, n)); -1 / NaN past the last candidate."""
+        n = capi.doc_nearest_n(n)
+        m = capi.doc_metric(metric)
+        theta, counts = capi.doc_queries(theta, counts, self.numTopics)
+        q = theta if theta is not None else counts
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, dtype=np.int64).reshape(-1)
+            if len(sk) != len(q):
+                raise ValueError(f"skip must hold one id per query ({len(q)}), not {len(sk)}")
+        ids = np.zeros((len(q), n), np.int64)
+        values = np.zeros((len(q), n), np.float64)
+        _check(self._L.ldatm_nearest_documents(self._h, m, n, len(q), theta.ctypes.data if theta is not None else None,
+                                               counts.ctypes.data if counts is not None else None,
+                                               sk.ctypes.data if sk is not None and len(sk) else None, int(minTokens),
+                                               ids.ctypes.data, values.ctypes.data), "nearestDocuments")
+        return ids, values
+
+    def documentNeighbors(self, n: int = 10, docs=None, metric="hellinger", minTokens: int = 1):
+        """ldatm_document_neighbors: per training document of `docs` (global
+        ids; None = all) its n nearest other documents with at least minTokens
+        tokens, rows built and neighbours selected on the device.  Returns
+        (ids int64 (M, n), values float64 (M, n)); -1 / NaN past the last
+        candidate."""
+        n = capi.doc_nearest_n(n)
+        m = capi.doc_metric(metric)
+        q, M = _doc_ids(docs, self)
+        ids = np.zeros((M, n), np.int64)
+        values = np.zeros((M, n), np.float64)
+        _check(self._L.ldatm_document_neighbors(self._h, m, n, M, q.ctypes.data if q is not None and M else None,
+                                                int(minTokens), ids.ctypes.data, values.ctypes.data),
+               "documentNeighbors")
+        return ids, values
+
+    def getDocumentNeighbors(self, doc: int, n: int = 10, metric="hellinger", minTokens: int = 1) -> list:
+        """The neighbours of one document as [(doc id, name, value), ...],
+        nearest first; name is the instance's name (None without one)."""
+        ids, values = self.documentNeighbors(n, [int(doc)], metric, minTokens)
+        name = lambda d: self.data[d].name if d < len(self.data) else None
+        return [(int(d), name(int(d)), float(v)) for d, v in zip(ids[0], values[0]) if d >= 0]
+
+    def documentNeighborsText(self, n: int = 10, metric="hellinger", minTokens: int = 1) -> str:
+        """printDocumentNeighbors' text: "#doc neighbor name value", then per
+        document and rank "doc neighbor name value"."""
+        n, m = capi.doc_nearest_n(n), capi.doc_metric(metric)
+        return self._text(self._L.ldatm_document_neighbors_text, n, m, int(minTokens))
+
+    def printDocumentNeighbors(self, path, n: int = 10, metric="hellinger", minTokens: int = 1):
+        n, m = capi.doc_nearest_n(n), capi.doc_metric(metric)
+        _check(self._L.ldatm_print_document_neighbors(self._h, os.fsencode(path), n, m, int(minTokens)),
+               "printDocumentNeighbors")
 
     # ------------------------------------------------ held-out evaluation
     def getHeldOutEvaluator(self) -> "HeldOutEvaluator":
@@ -1835,6 +1946,15 @@ class TopicInferencer:
                                          ids.ctypes.data if ids is not None and M else None,
                                          scores.ctypes.data, theta.ctypes.data), "scoreInstances")
         return scores, theta
+
+    def nearestInstances(self, instances, n: int = 10, metric="hellinger", numIterations: int = 100,
+                         thinning: int = 10, burnIn: int = 10, seed: int = 0, minTokens: int = 1):
+        """getSampledDistributions of `instances`, then the model's
+        nearestDocuments of those rows: (docs[Q, n], values[Q, n])."""
+        n = capi.doc_nearest_n(n)
+        m = capi.doc_metric(metric)
+        theta = self.getSampledDistributions(instances, numIterations, thinning, burnIn, seed)
+        return self.model.nearestDocuments(theta, n, m, minTokens)
 
     def getSampledDistribution(self, instance, numIterations: int = 100, thinning: int = 10,
                                burnIn: int = 10, seed: int = 0) -> np.ndarray:
