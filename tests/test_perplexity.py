@@ -109,7 +109,7 @@ def test_heldout_perplexity_within_1pct(oracle, K):
     K = 2048 / 4096 (round 6, VERDICT r5 missing #2): the large-K sparse
     sampler k_sample_big (C = 32 / 64), whose round-5 draw -- the exact
     fixed-point doc part and the own-entry accept / re-draw --
-    had only a per-draw chi-square test behind it; 16 seeds each against the
+    had only a per-draw chi-square test behind it; 32 seeds each against the
     committed cpu_mallet fixture (tools/ppl_mallet_seeds.py, scored with the
     large-K inference draw), the same three bars."""
     from ldagibbssampling_amd.sampler import GibbsSampler
